@@ -27,10 +27,8 @@ import os
 import sys
 import time
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")  # one hardware queue per stream (see pienerf_amd/__init__.py); before HIP initialises
-
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+import numpy as np
+import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -44,6 +42,47 @@ MARCH_BYTES = dict(iteration=8, candidate=16, warp=64, sample=32 + 4, ray_trip=4
 HBM_PEAK_GBS = 8000.0               # MI355X_MICROARCH.md: HBM3E 8 TB/s
 F32_MFMA_PEAK_TF = 157.3            # dense fp32-input MFMA peak
 F16_MFMA_PEAK_TF = 2500.0           # dense fp16 / bf16 MFMA peak
+DUMP_LIMIT_BYTES = 64 << 20         # --dump-outputs: everything written, in all
+
+
+def frame_arrays(out, H, W):
+    """image [H, W, 3], depth [H, W], depth_0 [H, W] of one frame as host float arrays: `out` is what the timed path hands its caller (device
+    tensors with a leading batch dimension, or a pipeline result with host views of the pinned buffers beside the device tensors)."""
+    shapes = {"image": (H, W, 3), "depth": (H, W), "depth_0": (H, W)}
+    res = {}
+    for k, shp in shapes.items():
+        a = out[k] if k in out else out["device"][k]
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.array(a)   # np.array: a copy, pinned views are reused by later frames
+        res[k] = a.reshape(shp).astype(a.dtype if a.dtype in (np.float32, np.float64) else np.float32)
+    return res
+
+
+def finite_arrays(arrays):
+    """Every array with its non-finite entries set to 0, plus <name>_nonfinite (1 where the entry was NaN / inf) for each array that had any.
+    The render path returns NaN depth for rays that miss the scene box (nears == fars, as in the reference: 0 / 0); the mask keeps that
+    information while every file written holds finite values only."""
+    res = {}
+    for name, a in arrays.items():
+        bad = ~np.isfinite(a)
+        if bad.any():
+            res[name] = np.where(bad, 0, a).astype(a.dtype)
+            res[f"{name}_nonfinite"] = bad.astype(np.float32)
+        else:
+            res[name] = a
+    return res
+
+
+def dump_outputs(out_dir, arrays):
+    """Writes out_dir/<name>.npy for every array (finite values only, see finite_arrays); refuses to write more than DUMP_LIMIT_BYTES in all."""
+    arrays = finite_arrays(arrays)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES} byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return {"dir": out_dir, "files": {name: {"shape": list(a.shape), "dtype": str(a.dtype)} for name, a in arrays.items()}, "bytes": total,
+            "nonfinite_entries": {name[:-len("_nonfinite")]: int(a.sum()) for name, a in arrays.items() if name.endswith("_nonfinite")}}
 
 
 def cuda_time_ms(fn, iters=20, warmup=3):
@@ -545,11 +584,18 @@ def main():
                          "over ALL ranks + one all_gather_into_tensor (latency; frames.TileParallel; SURVEY 8e's alternative).  With N = 1 'tile' runs the same "
                          "eager one-frame-at-a-time path on one rank (PN_FORCE_DIST=1: inside a one-rank RCCL group, collectives included)")
     ap.add_argument("--sigma-gain", type=float, default=1.0, help="scales the synthetic checkpoint's density (samples per frame fall as it rises)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last timed frame's image / depth / depth_0 as DIR/<name>.npy, non-finite entries as 0 with a "
+                         "DIR/<name>_nonfinite.npy mask (rank 0; single GPU or --parallelism tile)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and world > 1 and args.parallelism != "tile":
+        ap.error("--dump-outputs: a frame-parallel run spreads its frames over the ranks; dump from a single-GPU or --parallelism tile run")
     rccl_ranks = None
     force_dist = world == 1 and os.environ.get("PN_FORCE_DIST", "") == "1"   # a process group of ONE rank (tests: RCCL itself on a one-GPU box)
     if force_dist:
@@ -595,6 +641,7 @@ def main():
         h.wait_frame_copies()   # the copier thread's SDMA copies are on no stream: the clock stops when the last frame enqueued has landed in host memory
 
     frames_done = [0]
+    last_out = [None]   # what the last step handed its caller (eager and tile-parallel forms)
     tile_mode = args.parallelism == "tile"
     if tile_mode:
         # every rank renders 1/world of each frame's 8 x 8 tiles from the owner's broadcast DOF snapshot; one all-gather hands every rank the frame.
@@ -608,7 +655,7 @@ def main():
 
         def run_steps(n):
             for _ in range(n):
-                o_ = h.step_tile_parallel()
+                o_ = last_out[0] = h.step_tile_parallel()
                 if copy_out and rank == 0:
                     h.to_host(o_)
             frames_done[0] += n
@@ -617,7 +664,7 @@ def main():
         if args.eager:
             def run_steps(n):
                 for _ in range(n):
-                    o_ = h.step()
+                    o_ = last_out[0] = h.step()
                     if copy_out:
                         h.to_host(o_)
             launch = "eager (one kernel launch per host call)"
@@ -699,14 +746,21 @@ def main():
         if tile_mode:
             pass
         elif world > 1 or not (args.eager or args.single_graph):  # the last frames in flight are retired here
-            frames_done[0] += len(h.drain_pipeline())
+            drained = h.drain_pipeline()
+            frames_done[0] += len(drained)
             continued = h._pipe_backend.continued
+            last_out[0] = next((r for f, r in drained if f == h._pipe.last_frame), None)
             # ... and the last frame the pipeline delivered is rendered again, launch by launch, from the state its workspace holds: bit for bit
             if h._pipe.last_ws is not None:
                 verified = h.verify_last_frame()
         elif args.single_graph:
-            h._check_previous_graph_frame()
+            last_out[0] = h.finish_graph_frame()
             continued = getattr(h, "graph_continued", 0)
+        dumped = None
+        if args.dump_outputs and rank == 0:
+            if last_out[0] is None:
+                raise RuntimeError("--dump-outputs: the timed steps delivered no frame on this rank")
+            dumped = dump_outputs(args.dump_outputs, frame_arrays(last_out[0], opt["H"], opt["W"]))
     per_rank_frames = None
     if world > 1:
         t = torch.tensor([elapsed, elapsed_unprimed], dtype=torch.float64, device=dev)
@@ -759,6 +813,9 @@ def main():
             "roofline": roofline,
         }
         res.update(extra)
+        if dumped is not None:
+            res["dumped_outputs"] = dict(dumped, note="the last timed step's frame, as the timed path delivered it to its caller; non-finite entries written as 0 "
+                                                      "and marked 1 in <name>_nonfinite.npy (depth of rays that miss the scene box is NaN)")
         # what bounds the frame-parallel job: the sim owner's substep rate — the simulator is time-sequential — against N (or N - 1
         # with a dedicated owner) ranks rendering at the single-GPU rate
         t_launch, t_coop = extra["breakdown_ms"]["stepforward_alone"], extra["breakdown_ms"]["stepforward_persistent_alone"]

@@ -13,7 +13,6 @@ import time
 
 import torch
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pienerf_amd import scene  # noqa: E402
 from pienerf_amd.harness import SimRenderHarness  # noqa: E402
