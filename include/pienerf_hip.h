@@ -409,8 +409,17 @@ int pn_sim_update_F(int n_IP, const int* topo, const double* dof, const double* 
                     float* dF, void* stream);
 
 /* calc_elastic (simulator/cuda_utils.py:83-121) + volume_invariant_project (simulator/func_utils.py:21-40).
- * RF, VF [n_IP,3,3] fp64 row-major; FF may be NULL. */
-int pn_sim_calc_elastic(int n_IP, const int* topo, const double* dNx, const double* dof, double* RF, double* VF, double* FF, void* stream);
+ * RF, VF [n_IP,3,3] fp64 row-major; FF may be NULL.
+ * mcadams_sweeps (here and in pn_sim_stepforward / pn_sim_stepforward_cells): which decomposition stands in for wp.svd3 (simulator/cuda_utils.py:107;
+ * warp-lang is third-party and absent), for this call only:
+ *   0            converged Jacobi — the contract: U, V proper rotations, the sign of det F on the last singular value;
+ *   n in 1..64   the published algorithm wp.svd3 implements (McAdams et al., UW-Madison TR1690) with n fixed Jacobi sweeps, approximate Givens
+ *                quaternions, negating-swap sort, Givens-quaternion QR, the paper's 10-digit constants (8 = double-precision setting, 4 = the paper's
+ *                single-precision one).  oracle/sim_oracle.cpp: svd3_mcadams is the CPU restatement it is tested against;
+ *   otherwise    PN_ERR_ARG.
+ * pn_sim_stepforward_coop has the converged Jacobi only. */
+int pn_sim_calc_elastic(int n_IP, const int* topo, const double* dNx, const double* dof, double* RF, double* VF, double* FF, int mcadams_sweeps,
+                        void* stream);
 
 /* collect_rhs_IP (simulator/cuda_utils.py:124-151) in its deterministic gather form (the reference ships the same
  * idea unused: collect_rhs_kernel :153-188, CSR built at solver.py:284-313).  csr_bg/csr_cnt [n_k], csr_buf [8 n_IP]
@@ -426,12 +435,12 @@ int pn_sim_matvec3(int n, const double* A, const double* X, double* Y, void* str
  * All vectors [10 n_k,3] fp64.  dof and dof_vel are updated in place.  work: >= pn_sim_work_doubles(n_k, n_IP) doubles.
  * prepared != 0: pn_sim_prepare has run on this `work` (the gather's chunk layout is there, and the per-IP rotations the local step's SVD is
  * warm-started from — they carry over from one local/global iteration and substep to the next); 0: the layout is rebuilt in this call and every
- * SVD starts from the identity. */
+ * SVD starts from the identity.  mcadams_sweeps: the decomposition, see pn_sim_calc_elastic. */
 int pn_sim_stepforward(int n_k, int n_IP, int iters, double dt, double dx, const int* topo, const int* csr_bg, const int* csr_cnt,
                        const int* csr_buf, const double* mu, const double* lam, const double* dNx, const double* dNx_csr, const int* csr_pos,
                        const double* Ainv,
                        const double* Mmat, const double* dof_rest, const double* rhs_rest, const double* rhs_gravity, const double* dof_f,
-                       double* dof, double* dof_vel, double* work, int prepared, void* stream);
+                       double* dof, double* dof_vel, double* work, int prepared, int mcadams_sweeps, void* stream);
 /* dNx_csr (may be NULL): dNx rows gathered in CSR order, dNx_csr[e] = dNx[csr_buf[e]] (30 doubles each), built once at
  * initialisation; with it collect_rhs streams contiguous memory (one workgroup per kernel) instead of chasing csr_buf.
  * csr_pos (may be NULL; needs dNx_csr): inverse of csr_buf, csr_pos[csr_buf[e]] = e; calc_elastic then also writes P once per
@@ -453,22 +462,13 @@ uint64_t pn_sim_work_doubles(int n_k, int n_IP);
  * the previous local/global iteration, kept in `work`) makes a substep's bits depend on the step HISTORY: bit-reproducible run to run for identical
  * histories; whoever restores dof / dof_vel to replay a trajectory bit for bit re-runs pn_sim_cells_prepare (Simulator.reset_warm_start) as well.
  * work >= pn_sim_cells_work_doubles doubles, initialised once by pn_sim_cells_prepare (identity rotations for the warm-started SVD, arrival counters). */
-/* Which decomposition stands in for wp.svd3 (simulator/cuda_utils.py:107; warp-lang is third-party and absent) in calc_elastic, for every substep /
- * calc_elastic call ENQUEUED after it (process-global; a captured graph keeps the choice it was captured with):
- *   0 (default)  converged Jacobi — the contract: U, V proper rotations, the sign of det F on the last singular value;
- *   n in 1..64   the published algorithm wp.svd3 implements (McAdams et al., UW-Madison TR1690) with n fixed Jacobi sweeps, approximate Givens
- *                quaternions, negating-swap sort, Givens-quaternion QR, the paper's 10-digit constants (8 = double-precision setting, 4 = the paper's
- *                single-precision one).  pn_sim_stepforward, pn_sim_stepforward_cells and pn_sim_calc_elastic honour it; pn_sim_stepforward_coop
- *                returns PN_ERR_ARG while it is set.  oracle/sim_oracle.cpp: svd3_mcadams is the CPU restatement it is tested against. */
-int pn_sim_set_svd(int mcadams_sweeps);
-int pn_sim_get_svd(void);
 int pn_sim_cells_chunk_ips(void);
 uint64_t pn_sim_cells_work_doubles(int n_k, int n_chunks);
 int pn_sim_cells_prepare(int n_k, int n_chunks, double* work, void* stream);
 int pn_sim_stepforward_cells(int n_k, int n_chunks, int iters, double dt, double dx, const int* chunk_tab, const double* dNx_cell, const double* mu_cell,
                              const double* lam_cell, const int* kp_bg, const int* kp_pos, const double* Ainv, const double* Mmat, const double* dof_rest,
                              const double* rhs_rest, const double* rhs_gravity, const double* dof_f, double* dof, double* dof_vel, double* work,
-                             void* stream);
+                             int mcadams_sweeps, void* stream);
 /* The local/global iterations of a substep as ONE persistent kernel of n_wg workgroups (one per CU; csrc/pn_sim.hip: k_substep_coop) instead of four
  * launches per iteration: same arguments and results as pn_sim_stepforward (tolerance of the summation orders, ~1e-13 relative), `work` prepared by
  * pn_sim_prepare, `coop` >= pn_sim_coop_bytes(n_k, n_IP, n_wg) bytes prepared by pn_sim_coop_prepare, which also returns plan[3] = {pieces, entries

@@ -88,17 +88,15 @@ SIGNATURES = {
     "pn_net_form_epoch": (i32, [P]),
     "pn_frame_trip_records": (i32, [P, P, P, i32, P]),
     "pn_sim_update_F": (i32, [i32, P, P, P, P, P, P, P, P, P]),
-    "pn_sim_calc_elastic": (i32, [i32, P, P, P, P, P, P, P]),
+    "pn_sim_calc_elastic": (i32, [i32, P, P, P, P, P, P, i32, P]),
     "pn_sim_collect_rhs": (i32, [i32, f64, P, P, P, P, P, P, P, P, P, P]),
     "pn_sim_matvec3": (i32, [i32, P, P, P, P]),
-    "pn_sim_stepforward": (i32, [i32, i32, i32, f64, f64, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, i32, P]),
+    "pn_sim_stepforward": (i32, [i32, i32, i32, f64, f64, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, i32, i32, P]),
     "pn_sim_prepare": (i32, [i32, i32, P, P, P, P]),
-    "pn_sim_set_svd": (i32, [i32]),
-    "pn_sim_get_svd": (i32, []),
     "pn_sim_cells_chunk_ips": (i32, []),
     "pn_sim_cells_work_doubles": (u64, [i32, i32]),
     "pn_sim_cells_prepare": (i32, [i32, i32, P, P]),
-    "pn_sim_stepforward_cells": (i32, [i32, i32, i32, f64, f64, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "pn_sim_stepforward_cells": (i32, [i32, i32, i32, f64, f64, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, i32, P]),
     "pn_sim_work_doubles": (u64, [i32, i32]),
     "pn_sim_coop_bytes": (u64, [i32, i32, i32]),
     "pn_sim_coop_prepare": (i32, [i32, i32, i32, P, P, P, C.POINTER(i32), P]),

@@ -314,15 +314,9 @@ __device__ __forceinline__ double shfl_xor_d(double v, int m) {
 
 }  // namespace
 
-// Which svd3 the substep kernels run: 0 = the converged, warm-started threshold Jacobi (default); n > 0 = McAdams' algorithm with n sweeps
-// (PN_SIM_SVD=mcadams[:n] on the Python side).  Process-global, read when a substep is enqueued (or captured into a graph).
-static int g_pn_svd_mc_sweeps = 0;
-extern "C" int pn_sim_set_svd(int mcadams_sweeps) {
-    PN_REQUIRE(mcadams_sweeps >= 0 && mcadams_sweeps <= 64);
-    g_pn_svd_mc_sweeps = mcadams_sweeps;
-    return PN_OK;
-}
-extern "C" int pn_sim_get_svd(void) { return g_pn_svd_mc_sweeps; }
+// mcadams_sweeps, the argument of every entry that runs calc_elastic: which svd3 its kernels run.  0 = the converged, warm-started threshold Jacobi
+// (default); 1..64 = McAdams' algorithm with that many sweeps (PN_SIM_SVD=mcadams[:n] on the Python side); anything else is PN_ERR_ARG.
+static inline bool pn_svd_sweeps_ok(int mcadams_sweeps) { return mcadams_sweeps >= 0 && mcadams_sweeps <= 64; }
 
 #ifndef PN_SIM_STAMPS
 #define PN_SIM_STAMPS 0
@@ -426,7 +420,7 @@ template <bool MC = false>
 __global__ void __launch_bounds__(256) k_elastic(int n_IP, const int* __restrict__ topo, const double* __restrict__ dNx, const double* __restrict__ dof,
                                                  double* __restrict__ RF, double* __restrict__ VF, double* __restrict__ FF, double* __restrict__ P,
                                                  const double* __restrict__ mu, const double* __restrict__ lam, double dx3,
-                                                 const int* __restrict__ csr_pos = nullptr, double* __restrict__ P_csr = nullptr, int dbg_nosvd = 0,
+                                                 const int* __restrict__ csr_pos = nullptr, double* __restrict__ P_csr = nullptr,
                                                  double* __restrict__ Vstore = nullptr, int mc_sweeps = 0) {
     PN_SIM_STAMP(1);
     PN_SIM_PRIO();
@@ -469,13 +463,7 @@ __global__ void __launch_bounds__(256) k_elastic(int n_IP, const int* __restrict
     if (i == 0) {
         M3 U, V;
         double sig[3], sp[3];
-        if (dbg_nosvd) {  // timing experiment (PN_SIM_DBG_NOSVD=1): results invalid
-#pragma unroll
-            for (int r = 0; r < 3; r++)
-#pragma unroll
-                for (int c = 0; c < 3; c++) { U.m[r][c] = (r == c); V.m[r][c] = (r == c); }
-            sig[0] = Fm.m[0][0]; sig[1] = Fm.m[1][1]; sig[2] = Fm.m[2][2];
-        } else if (MC) {
+        if (MC) {
             svd3_mcadams(Fm, U, sig, V, mc_sweeps);   // the published algorithm: fixed sweeps, no warm start
         } else if (Vstore) {
             // step driver: start from this IP's V of the previous local/global iteration (identity before the first substep), leave the new one.
@@ -523,11 +511,11 @@ __global__ void __launch_bounds__(256) k_elastic(int n_IP, const int* __restrict
 }
 
 extern "C" int pn_sim_calc_elastic(int n_IP, const int* topo, const double* dNx, const double* dof, double* RF, double* VF, double* FF,
-                                   void* stream) {
-    PN_REQUIRE(n_IP > 0 && topo && dNx && dof && RF && VF);
-    if (g_pn_svd_mc_sweeps)
+                                   int mcadams_sweeps, void* stream) {
+    PN_REQUIRE(n_IP > 0 && topo && dNx && dof && RF && VF && pn_svd_sweeps_ok(mcadams_sweeps));
+    if (mcadams_sweeps)
         k_elastic<true><<<pn_div_up((uint64_t)n_IP * 8, 256), 256, 0, (hipStream_t)stream>>>(n_IP, topo, dNx, dof, RF, VF, FF, nullptr, nullptr, nullptr, 0.0,
-                                                                                             nullptr, nullptr, 0, nullptr, g_pn_svd_mc_sweeps);
+                                                                                             nullptr, nullptr, nullptr, mcadams_sweeps);
     else
         k_elastic<false><<<pn_div_up((uint64_t)n_IP * 8, 256), 256, 0, (hipStream_t)stream>>>(n_IP, topo, dNx, dof, RF, VF, FF, nullptr, nullptr, nullptr, 0.0);
     PN_LAUNCH_CHECK();
@@ -654,7 +642,7 @@ __global__ void __launch_bounds__(1024) k_rhs_gather_csr(int n_k, const int* __r
 // Balanced form of the gather used by the step driver.  One workgroup per kernel leaves the launch as long as its longest list (chair:
 // 770 entries against a mean of 206, and only 139 of 256 CUs busy), so the lists are cut into chunks of PN_GCH entries, one
 // workgroup per chunk, each writing its 30 partial sums; the chunk sums of a kernel are added in ascending chunk order by the
-// consumer (k_matvec3_gathered builds its X operand from them in LDS), so the result is still reproducible bit for bit.
+// workgroup that completes its kernel's set (k_rhs_gather_chunk), so the result is still reproducible bit for bit.
 // k_gather_plan (once per simulator, one workgroup) lays the chunks out: kc_bg[k] = first chunk of kernel k, chunk[b] = (first entry, count, kernel,
 // chunks of that kernel); every kernel gets at least one chunk (an empty one if it has no entries), unused grid slots have kernel -1.
 #ifndef PN_GCH
@@ -700,8 +688,8 @@ __global__ void __launch_bounds__(512) k_gather_plan(int n_k, int chunks_max, co
     for (int b = n_chunks + threadIdx.x; b < chunks_max; b += blockDim.x) chunk[b] = make_int4(0, 0, -1, 0);  // unused tail of the grid
 }
 
-// `tot` != nullptr: the workgroup that completes its kernel's set of chunks ("last arriver") also adds them up, in ascending chunk order like
-// k_gather_sum, and writes momentum + sum - rhs_rest: one launch less per local/global iteration (of the 4).  The XCDs' L2s are not coherent with each
+// The workgroup that completes its kernel's set of chunks ("last arriver") also adds them up, in ascending chunk order, and writes
+// momentum + sum - rhs_rest: the sums need no launch of their own.  The XCDs' L2s are not coherent with each
 // other, so the chunk sums go out as agent-scope stores (written through to the memory side), a workgroup waits for their acknowledgement before it bumps
 // its kernel's arrival counter (agent-scope atomic at the memory side), and the last arriver — the one that counts `chunks` arrivals — reads all sums
 // with agent-scope loads and stores 0 back into the counter: nobody else arrives at it before the next launch, so the counter is cyclic and a simulator
@@ -748,12 +736,8 @@ __global__ void __launch_bounds__(PN_GCH * 8) k_rhs_gather_chunk(const int4* __r
         double s = (red[sl][x][r] + red[sl][10 + x][r]) + red[sl][20 + x][r];
 #pragma unroll
         for (int m = NS / 2; m > 0; m >>= 1) s += shfl_xor_d(s, m);
-        if (sl == 0) {
-            if (tot) __hip_atomic_store(part + (size_t)b * 30 + o, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            else part[(size_t)b * 30 + o] = s;
-        }
+        if (sl == 0) __hip_atomic_store(part + (size_t)b * 30 + o, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    if (!tot) return;
     __builtin_amdgcn_s_waitcnt(0);  // the sums are at the memory side
     __syncthreads();
     if (t == 0) {
@@ -774,19 +758,6 @@ __global__ void __launch_bounds__(PN_GCH * 8) k_rhs_gather_chunk(const int4* __r
     }
     const size_t o = (size_t)kern * 30 + t;
     tot[o] = momentum[o] + sum - rhs_rest[o];
-}
-
-// out = momentum + (chunk sums of the row's kernel, ascending chunk order) - rhs_rest: one thread per output row
-__global__ void __launch_bounds__(256) k_gather_sum(int n30, const int* __restrict__ kc_bg, const double* __restrict__ part,
-                                                    const double* __restrict__ momentum, const double* __restrict__ rhs_rest, double* __restrict__ out) {
-    PN_SIM_PRIO();
-    const int o = blockIdx.x * blockDim.x + threadIdx.x;
-    if (o >= n30) return;
-    const int k = o / 30, q = o - k * 30;
-    const int b0 = kc_bg[k], b1 = kc_bg[k + 1];
-    double sum = 0.0;
-    for (int b = b0; b < b1; b++) sum += part[(size_t)b * 30 + q];
-    out[o] = momentum[o] + sum - rhs_rest[o];
 }
 
 extern "C" int pn_sim_collect_rhs(int n_k, double dx, const int* csr_bg, const int* csr_cnt, const int* csr_buf, const double* mu, const double* lam,
@@ -860,60 +831,6 @@ __global__ void __launch_bounds__(256) k_matvec3(int n, const double* __restrict
     }
 }
 
-// dof = dof_rest + Ainv @ (momentum + gathered - rhs_rest) with the right-hand side assembled in LDS from the chunk sums of
-// k_rhs_gather_chunk (ascending chunk order per kernel: a fixed summation tree).  The matrix rows stream from L2 exactly as in
-// k_matvec3; X comes from LDS instead of four L2 reads of the whole vector per workgroup.
-__global__ void __launch_bounds__(256) k_matvec3_gathered(int n, const double* __restrict__ A, double* __restrict__ Y, const double* __restrict__ add1,
-                                                          const double* __restrict__ momentum, const double* __restrict__ rhs_rest,
-                                                          const double* __restrict__ part, const int* __restrict__ kc_bg) {
-    PN_SIM_PRIO();
-    extern __shared__ double xs[];  // [n * 3]
-    for (int o = threadIdx.x; o < n * 3; o += 256) {
-        const int k = o / 30, q = o - k * 30;
-        double sum = 0.0;
-        for (int b = kc_bg[k]; b < kc_bg[k + 1]; b++) sum += part[(size_t)b * 30 + q];
-        xs[o] = momentum[o] + sum - rhs_rest[o];
-    }
-    __syncthreads();
-    const int i0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 2;
-    if (i0 >= n) return;
-    const bool two = i0 + 1 < n;
-    const int lane = threadIdx.x & 63;
-    const double* __restrict__ a = A + (size_t)i0 * n;
-    const double* __restrict__ b = A + (size_t)(two ? i0 + 1 : i0) * n;
-    double s[6] = {0, 0, 0, 0, 0, 0};
-    int j = lane;
-    for (; j + 192 < n; j += 256) {
-        double wa[4], wb[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) { wa[u] = a[j + 64 * u]; wb[u] = b[j + 64 * u]; }
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const int jj = j + 64 * u;
-            const double x0 = xs[jj * 3], x1 = xs[jj * 3 + 1], x2 = xs[jj * 3 + 2];
-            s[0] += wa[u] * x0; s[1] += wa[u] * x1; s[2] += wa[u] * x2;
-            s[3] += wb[u] * x0; s[4] += wb[u] * x1; s[5] += wb[u] * x2;
-        }
-    }
-    for (; j < n; j += 64) {
-        const double wa = a[j], wb = b[j];
-        const double x0 = xs[j * 3], x1 = xs[j * 3 + 1], x2 = xs[j * 3 + 2];
-        s[0] += wa * x0; s[1] += wa * x1; s[2] += wa * x2;
-        s[3] += wb * x0; s[4] += wb * x1; s[5] += wb * x2;
-    }
-#pragma unroll
-    for (int q = 0; q < 6; q++)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s[q] += shfl_xor_d(s[q], o);
-    if (lane < (two ? 6 : 3)) {
-        double v = 0.0;
-#pragma unroll
-        for (int q = 0; q < 6; q++) if (q == lane) v = s[q];
-        const size_t o = (size_t)i0 * 3 + lane;
-        Y[o] = add1[o] + v;
-    }
-}
-
 extern "C" int pn_sim_matvec3(int n, const double* A, const double* X, double* Y, void* stream) {
     PN_REQUIRE(n > 0 && A && X && Y);
     k_matvec3<<<pn_div_up(n, 8), 256, 0, (hipStream_t)stream>>>(n, A, X, Y, 0, nullptr, nullptr);
@@ -984,9 +901,10 @@ extern "C" int pn_sim_prepare(int n_k, int n_IP, const int* csr_bg, const int* c
 extern "C" int pn_sim_stepforward(int n_k, int n_IP, int iters, double dt, double dx, const int* topo, const int* csr_bg, const int* csr_cnt,
                                   const int* csr_buf, const double* mu, const double* lam, const double* dNx, const double* dNx_csr,
                                   const int* csr_pos, const double* Ainv, const double* Mmat, const double* dof_rest, const double* rhs_rest,
-                                  const double* rhs_gravity, const double* dof_f, double* dof, double* dof_vel, double* work, int prepared, void* stream) {
+                                  const double* rhs_gravity, const double* dof_f, double* dof, double* dof_vel, double* work, int prepared, int mcadams_sweeps,
+                                  void* stream) {
     PN_REQUIRE(n_k > 0 && n_IP > 0 && iters >= 0 && topo && csr_bg && csr_cnt && csr_buf && mu && lam && dNx && Ainv && Mmat);
-    PN_REQUIRE(dof_rest && rhs_rest && rhs_gravity && dof_f && dof && dof_vel && work);
+    PN_REQUIRE(dof_rest && rhs_rest && rhs_gravity && dof_f && dof && dof_vel && work && pn_svd_sweeps_ok(mcadams_sweeps));
     hipStream_t st = (hipStream_t)stream;
     const int n = n_k * 10, n3 = n * 3;
     double* tilde = work;
@@ -1002,69 +920,42 @@ extern "C" int pn_sim_stepforward(int n_k, int n_IP, int iters, double dt, doubl
     int4* chunk = gp.chunk;
     const double dx3 = pow(dx, 3.0);
     const bool pcsr = dNx_csr && csr_pos;
-    // balanced gather (chunked lists + right-hand side assembled inside the matvec); PN_SIM_GATHER=kernel keeps one workgroup per kernel
-    static const bool chunked_ok = [] { const char* v = getenv("PN_SIM_GATHER"); return !(v && strcmp(v, "kernel") == 0); }();
-    static const bool fused_x = [] { const char* v = getenv("PN_SIM_GATHER"); return v && strcmp(v, "fused") == 0; }();
-    static const int dbg_nosvd = (int)pn_env_u32("PN_SIM_DBG_NOSVD", 0);
-    static const bool fuse_sum = [] { const char* v = getenv("PN_SIM_FUSE_SUM"); return !(v && v[0] == '0'); }();  // the chunk kernel's last arriver sums (0: k_gather_sum)
+    // balanced gather: the lists cut into chunks of PN_GCH entries, the chunk kernel's last arriver sums them.  Without the CSR-ordered copies, or for a
+    // right-hand side above ~159 KB, one gather workgroup per kernel instead (k_rhs_gather_csr / k_rhs_gather)
+    const bool chunked = pcsr && (size_t)n3 * sizeof(double) <= 160 * 1024 - 1024;
+    if (chunked && !prepared) k_gather_plan<<<1, 512, 0, st>>>(n_k, (int)chunks_max, csr_bg, csr_cnt, kc_bg, chunk, gp.kcount);
+    double* Vstore = prepared ? pn_sim_vstore(work, n_k, n_IP) : nullptr;   // warm-started SVD (prepared == 0: every SVD starts from the identity)
     // k_elastic in one-wave workgroups: a lane's 60 loads (its kernel's 30 DOFs, its 30 shape-function gradients) are 240-B blocks of its own, so every
     // load instruction touches 64 cache lines and keeps the CU's address path busy for ~140 cycles; with 256-thread workgroups the 447 waves of the
     // chair sat four to a CU on 112 of the 256 CUs and queued on that path (31.9 -> 28.3 us per local/global iteration; 16-byte loads on top: nothing)
-    static const uint32_t el_wg = std::min(std::max(pn_env_u32("PN_SIM_EL_WG", 64) & ~63u, 64u), 256u);
-    // ... and the matrix products in one-wave workgroups as well: beside the render lanes' persistent workgroups a launch starts when its workgroups find
-    // room, and a single wave finds it sooner than four (start-to-start gap behind k_matvec3 in the pipeline: profiles/r04_sim_stamps.txt)
-    static const uint32_t mv_wg = std::min(std::max(pn_env_u32("PN_SIM_MV_WG", 64) & ~63u, 64u), 256u);
-    const size_t xs_bytes = (size_t)n3 * sizeof(double);
-    const bool chunked = pcsr && chunked_ok && xs_bytes <= 160 * 1024 - 1024;
-    if (chunked) {
-        if (xs_bytes > 48 * 1024 && fused_x) {  // dynamic LDS above 48 KB is opted into per DEVICE, so the cache is per device too
-            static size_t granted[PN_MAX_DEVICES] = {0};
-            int dev_id = 0;
-            PN_HIP_CHECK(hipGetDevice(&dev_id));
-            if (dev_id < 0 || dev_id >= PN_MAX_DEVICES || xs_bytes > granted[dev_id]) {
-                PN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_matvec3_gathered), hipFuncAttributeMaxDynamicSharedMemorySize, (int)xs_bytes));
-                if (dev_id >= 0 && dev_id < PN_MAX_DEVICES) granted[dev_id] = xs_bytes;
-            }
-        }
-        if (!prepared) k_gather_plan<<<1, 512, 0, st>>>(n_k, (int)chunks_max, csr_bg, csr_cnt, kc_bg, chunk, gp.kcount);
-    }
-    static const bool warm_svd = pn_env_u32("PN_SIM_COLD_SVD", 0) == 0;  // experiments: PN_SIM_COLD_SVD=1 starts every SVD from the identity (rounds 1-2)
-    double* Vstore = (prepared && warm_svd) ? pn_sim_vstore(work, n_k, n_IP) : nullptr;
-    // the substep's two elementwise launches ride on the matrix products next to them (PN_SIM_FUSE_ENDS=0: k_step_begin / k_step_end as launches)
-    static const bool fuse_ends = [] { const char* v = getenv("PN_SIM_FUSE_ENDS"); return !(v && v[0] == '0'); }();
-    const bool ends = fuse_ends && chunked && !fused_x && iters >= 1;
+    const uint32_t el_blocks = pn_div_up((uint64_t)n_IP * 8, 64);
+    // ... and the matrix products in one-wave workgroups (two rows each) as well: beside the render lanes' persistent workgroups a launch starts when its
+    // workgroups find room, and a single wave finds it sooner than four (start-to-start gap behind k_matvec3 in the pipeline: profiles/r04_sim_stamps.txt)
+    const uint32_t mv_blocks = pn_div_up(n, 2);
+    // the substep's two elementwise launches ride on the matrix products next to them; k_step_begin / k_step_end as launches when the gather is not
+    // chunked or there is no iteration to carry the epilogue
+    const bool ends = chunked && iters >= 1;
     if (ends) {
-        k_matvec3<<<pn_div_up(n, 2 * (mv_wg / 64)), mv_wg, 0, st>>>(n, Mmat, dof, momentum, 1, dof_f, rhs_gravity, dof_vel, dt, last);  // dof_tilde on the fly, dof_last = dof
+        k_matvec3<<<mv_blocks, 64, 0, st>>>(n, Mmat, dof, momentum, 1, dof_f, rhs_gravity, dof_vel, dt, last);  // dof_tilde on the fly, dof_last = dof
     } else {
         k_step_begin<<<pn_div_up(n3, 256), 256, 0, st>>>(n3, dt, dof, dof_vel, tilde, last);
-        k_matvec3<<<pn_div_up(n, 2 * (mv_wg / 64)), mv_wg, 0, st>>>(n, Mmat, tilde, momentum, 1, dof_f, rhs_gravity);  // compute_momentum (:574-576)
+        k_matvec3<<<mv_blocks, 64, 0, st>>>(n, Mmat, tilde, momentum, 1, dof_f, rhs_gravity);  // compute_momentum (:574-576)
     }
     for (int it = 0; it < iters; it++) {
-        if (g_pn_svd_mc_sweeps)
-            k_elastic<true><<<pn_div_up((uint64_t)n_IP * 8, el_wg), el_wg, 0, st>>>(n_IP, topo, dNx, dof, nullptr, nullptr, nullptr, pcsr ? nullptr : P, mu, lam,
-                                                                                dx3, pcsr ? csr_pos : nullptr, pcsr ? P_csr : nullptr, dbg_nosvd, Vstore,
-                                                                                g_pn_svd_mc_sweeps);
+        if (mcadams_sweeps)
+            k_elastic<true><<<el_blocks, 64, 0, st>>>(n_IP, topo, dNx, dof, nullptr, nullptr, nullptr, pcsr ? nullptr : P, mu, lam, dx3, pcsr ? csr_pos : nullptr,
+                                                      pcsr ? P_csr : nullptr, Vstore, mcadams_sweeps);
         else
-            k_elastic<false><<<pn_div_up((uint64_t)n_IP * 8, el_wg), el_wg, 0, st>>>(n_IP, topo, dNx, dof, nullptr, nullptr, nullptr, pcsr ? nullptr : P, mu, lam,
-                                                                                 dx3, pcsr ? csr_pos : nullptr, pcsr ? P_csr : nullptr, dbg_nosvd, Vstore);
-        if (chunked) {
-            const bool sum_in_chunk = fuse_sum && !fused_x;
-            k_rhs_gather_chunk<<<(uint32_t)chunks_max, PN_GCH * 8, 0, st>>>(chunk, dNx_csr, P_csr, part, gp.kcount, kc_bg, momentum, rhs_rest,
-                                                                            sum_in_chunk ? tot : nullptr);
-            if (fused_x) {
-                k_matvec3_gathered<<<pn_div_up(n, 8), 256, xs_bytes, st>>>(n, Ainv, dof, dof_rest, momentum, rhs_rest, part, kc_bg);
-            } else {
-                if (!sum_in_chunk) k_gather_sum<<<pn_div_up(n3, 256), 256, 0, st>>>(n3, kc_bg, part, momentum, rhs_rest, tot);
-                if (ends && it == iters - 1) k_matvec3<<<pn_div_up(n, 2 * (mv_wg / 64)), mv_wg, 0, st>>>(n, Ainv, tot, dof, 3, dof_rest, last, nullptr, dt, nullptr, dof_vel);
-                else k_matvec3<<<pn_div_up(n, 2 * (mv_wg / 64)), mv_wg, 0, st>>>(n, Ainv, tot, dof, 2, dof_rest, nullptr);
-            }
-            continue;
-        }
-        if (dNx_csr)  // CSR-ordered copy of dNx available: the coalesced one-workgroup-per-kernel gather
+            k_elastic<false><<<el_blocks, 64, 0, st>>>(n_IP, topo, dNx, dof, nullptr, nullptr, nullptr, pcsr ? nullptr : P, mu, lam, dx3, pcsr ? csr_pos : nullptr,
+                                                       pcsr ? P_csr : nullptr, Vstore);
+        if (chunked)
+            k_rhs_gather_chunk<<<(uint32_t)chunks_max, PN_GCH * 8, 0, st>>>(chunk, dNx_csr, P_csr, part, gp.kcount, kc_bg, momentum, rhs_rest, tot);
+        else if (dNx_csr)  // CSR-ordered copy of dNx available: the coalesced one-workgroup-per-kernel gather
             k_rhs_gather_csr<<<n_k, 1024, 0, st>>>(n_k, csr_bg, csr_cnt, csr_buf, dNx_csr, P, pcsr ? P_csr : nullptr, momentum, rhs_rest, tot);
         else
             k_rhs_gather<<<pn_div_up(n_k, 4), 256, 0, st>>>(n_k, dx3, csr_bg, csr_cnt, csr_buf, mu, lam, dNx, nullptr, nullptr, P, momentum, rhs_rest, tot);
-        k_matvec3<<<pn_div_up(n, 2 * (mv_wg / 64)), mv_wg, 0, st>>>(n, Ainv, tot, dof, 2, dof_rest, nullptr);  // x = G @ rhs ; dof = dof_rest + x (:600-601)
+        if (ends && it == iters - 1) k_matvec3<<<mv_blocks, 64, 0, st>>>(n, Ainv, tot, dof, 3, dof_rest, last, nullptr, dt, nullptr, dof_vel);  // + vel (:602)
+        else k_matvec3<<<mv_blocks, 64, 0, st>>>(n, Ainv, tot, dof, 2, dof_rest, nullptr);  // x = G @ rhs ; dof = dof_rest + x (:600-601)
     }
     if (!ends) k_step_end<<<pn_div_up(n3, 256), 256, 0, st>>>(n3, dt, dof, last, dof_vel);
     PN_LAUNCH_CHECK();
@@ -1320,9 +1211,9 @@ extern "C" int pn_sim_cells_prepare(int n_k, int n_chunks, double* work, void* s
 extern "C" int pn_sim_stepforward_cells(int n_k, int n_chunks, int iters, double dt, double dx, const int* chunk_tab, const double* dNx_cell,
                                         const double* mu_cell, const double* lam_cell, const int* kp_bg, const int* kp_pos, const double* Ainv,
                                         const double* Mmat, const double* dof_rest, const double* rhs_rest, const double* rhs_gravity, const double* dof_f,
-                                        double* dof, double* dof_vel, double* work, void* stream) {
+                                        double* dof, double* dof_vel, double* work, int mcadams_sweeps, void* stream) {
     PN_REQUIRE(n_k > 0 && n_chunks > 0 && iters >= 1 && chunk_tab && dNx_cell && mu_cell && lam_cell && kp_bg && kp_pos && Ainv && Mmat);
-    PN_REQUIRE(dof_rest && rhs_rest && rhs_gravity && dof_f && dof && dof_vel && work);
+    PN_REQUIRE(dof_rest && rhs_rest && rhs_gravity && dof_f && dof && dof_vel && work && pn_svd_sweeps_ok(mcadams_sweeps));
     hipStream_t st = (hipStream_t)stream;
     const int n = n_k * 10, n3 = n * 3;
     double* last = work;
@@ -1332,20 +1223,19 @@ extern "C" int pn_sim_stepforward_cells(int n_k, int n_chunks, int iters, double
     double* Vstore = part + (size_t)n_chunks * 240;
     int* kcount = reinterpret_cast<int*>(Vstore + (size_t)n_chunks * PN_CELL_IPS * 9);
     const double dx3 = pow(dx, 3.0);
-    static const uint32_t mv_wg = std::min(std::max(pn_env_u32("PN_SIM_MV_WG", 64) & ~63u, 64u), 256u);
-    const uint32_t mv_blocks = pn_div_up(n, 2 * (mv_wg / 64));
+    const uint32_t mv_blocks = pn_div_up(n, 2);   // one-wave workgroups of two rows, as in pn_sim_stepforward
     // compute_momentum with dof_tilde = dof + dt * vel on the fly and dof_last = dof (solver.py:574-576,597)
-    k_matvec3<<<mv_blocks, mv_wg, 0, st>>>(n, Mmat, dof, momentum, 1, dof_f, rhs_gravity, dof_vel, dt, last);
+    k_matvec3<<<mv_blocks, 64, 0, st>>>(n, Mmat, dof, momentum, 1, dof_f, rhs_gravity, dof_vel, dt, last);
     for (int it = 0; it < iters; it++) {
-        if (g_pn_svd_mc_sweeps)
+        if (mcadams_sweeps)
             k_cells_elastic_gather<true><<<n_chunks, PN_CELL_WAVES * 64, 0, st>>>(chunk_tab, reinterpret_cast<const double2*>(dNx_cell), mu_cell, lam_cell, dof,
                                                                                    dx3, Vstore, part, kcount, kp_bg, kp_pos, momentum, rhs_rest, tot,
-                                                                                   g_pn_svd_mc_sweeps);
+                                                                                   mcadams_sweeps);
         else
             k_cells_elastic_gather<false><<<n_chunks, PN_CELL_WAVES * 64, 0, st>>>(chunk_tab, reinterpret_cast<const double2*>(dNx_cell), mu_cell, lam_cell, dof,
                                                                                     dx3, Vstore, part, kcount, kp_bg, kp_pos, momentum, rhs_rest, tot, 0);
-        if (it == iters - 1) k_matvec3<<<mv_blocks, mv_wg, 0, st>>>(n, Ainv, tot, dof, 3, dof_rest, last, nullptr, dt, nullptr, dof_vel);  // + vel (:602)
-        else k_matvec3<<<mv_blocks, mv_wg, 0, st>>>(n, Ainv, tot, dof, 2, dof_rest, nullptr);                                                // :600-601
+        if (it == iters - 1) k_matvec3<<<mv_blocks, 64, 0, st>>>(n, Ainv, tot, dof, 3, dof_rest, last, nullptr, dt, nullptr, dof_vel);  // + vel (:602)
+        else k_matvec3<<<mv_blocks, 64, 0, st>>>(n, Ainv, tot, dof, 2, dof_rest, nullptr);                                                // :600-601
     }
     PN_LAUNCH_CHECK();
     return PN_OK;
@@ -1817,7 +1707,6 @@ extern "C" int pn_sim_stepforward_coop(int n_k, int n_IP, int iters, double dt, 
                                        double* dof_vel, double* work, void* coop, int n_wg, const int* plan, void* stream) {
     PN_REQUIRE(n_k > 0 && n_IP > 0 && iters >= 1 && iters <= PN_COOP_ITERS && topo && mu && lam && dNx && dNx_csr && csr_pos && Ainv && Mmat);
     PN_REQUIRE(dof_rest && rhs_rest && rhs_gravity && dof_f && dof && dof_vel && work && coop);
-    PN_REQUIRE(g_pn_svd_mc_sweeps == 0);  // the persistent form has the default decomposition only; PN_SIM_SVD=mcadams runs on the cell and CSR forms
     hipStream_t st = (hipStream_t)stream;
     PnCoopPlan pl;
     PN_REQUIRE(plan);

@@ -69,6 +69,8 @@ class Simulator:
         self.gravity = gravity.to(dtype=torchfloat).to(self.device)
         self.dof = None
         self._work = None
+        self._prepared = False   # pn_sim_prepare has run on _work (with the first substep: the CSR lists it reads are built by precompute)
+        self._cells = self._cells_work = None
         # stream on which update_force / clear_force are enqueued (None: the caller's current stream).  A harness that runs the substeps
         # on a stream of their own (harness.py: overlap_sim, capture_pipelined) sets it to that stream, so that a force change is ordered
         # BETWEEN two substeps instead of racing with one
@@ -101,14 +103,12 @@ class Simulator:
     def initialize(self):
         self.precompute()
         self._work = torch.empty(int(lib().pn_sim_work_doubles(self.n_k, self.n_IP)), dtype=torchfloat, device=self.device)
-        self._prepared = False  # pn_sim_prepare runs with the first substep (the CSR lists it reads are built further down)
-        if self.cell_form:
-            self._prepare_cells()
+        self._prepared = False
         self.rhs_rest = (self.build_rhs() + self._matvec(self.Mmat, self.dof)).contiguous()   # solver.py:314
 
     def precompute(self):
-        """Everything of initialize() that is tensor bookkeeping / torch.linalg (device-agnostic); the HIP-backed rest
-        state (rhs_rest) is finished by initialize()."""
+        """Everything of initialize() that is tensor bookkeeping / torch.linalg (device-agnostic), and on a GPU the cell form's work area for the
+        layout built here; the HIP-backed rest state (rhs_rest) is finished by initialize()."""
         dev, res, kres = self.device, self.res, self.kres
         r0, r1, r2 = (int(v) for v in res.cpu())
         self.grid_idx = ((self.pos - self.base) // self.dx).to(dtype=torch.int32).long()
@@ -173,7 +173,7 @@ class Simulator:
 
         self._IP2K = IP2K
         self._cells = self._cells_work = None
-        if self.cell_form:   # (torch bookkeeping only; the work area and the check against the library's chunk size: _prepare_cells)
+        if self.cell_form:   # (torch bookkeeping only; the work area and the check against the library's chunk size: _prepare_cells, below)
             self._build_cells()
 
         m = (self.IP_rho * self.dx * self.dx * self.dx)                                      # collect_gravity, cuda_utils.py:262-279
@@ -181,6 +181,8 @@ class Simulator:
         rows = (self.IP_kernel.long()[:, :, None] * 10 + torch.arange(10, device=dev)[None, None, :]).reshape(-1)
         gmls.index_add_ordered(rg, rows, (m[:, None, None] * self.IP_Nx).reshape(-1)[:, None] * self.gravity[None, :])
         self.rhs_gravity = rg.reshape(-1).contiguous()
+        if self._cells is not None and self.device.type == "cuda":   # a new layout gets a new work area, here and never inside a substep
+            self._prepare_cells()
 
     def _build_cells(self):
         """Layout of the substep's CELL form (include/pienerf_hip.h: pn_sim_stepforward_cells): the integration points of one kernel-grid cell share
@@ -224,7 +226,6 @@ class Simulator:
         pos[kp] = torch.arange(kp.numel(), device=dev)
         self._cells["kp_pos"] = pos.to(torch.int32).contiguous()                       # where (chunk, slot) stores its partial sum: its rank in its kernel's run
         self._cells["kp_bg"] = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(kcnt, 0)]).to(torch.int32).contiguous()
-        self._cells_work = None   # belongs to the layout: _prepare_cells() makes a new one (initialize(), or the first substep after a rebuild)
 
     def _prepare_cells(self):
         """The cell form's work area: identity rotations for the warm-started SVD, arrival counters (never inside a stream capture)."""
@@ -240,7 +241,7 @@ class Simulator:
         BIT-equal replays of a trajectory do: whoever restores dof / dof_vel to replay (harness.capture, tests) calls this as well."""
         if self._cells_work is not None:
             check(lib().pn_sim_cells_prepare(self.n_k, self._cells["n_chunks"], ptr(self._cells_work), stream_ptr()), "sim_cells_prepare")
-        if self._work is not None and self._prepared:
+        if self._prepared:
             check(lib().pn_sim_prepare(self.n_k, self.n_IP, ptr(self.kernel_bg), ptr(self.kernel_cnt), ptr(self._work), stream_ptr()), "sim_prepare")
 
     def collect_IP(self):  # solver.py:427-450
@@ -288,8 +289,8 @@ class Simulator:
         n = self.n_IP
         RF = torch.empty((n, 3, 3), dtype=torchfloat, device=self.device)
         VF = torch.empty_like(RF)
-        check(lib().pn_sim_set_svd(self.svd_sweeps), "sim_set_svd")
-        check(lib().pn_sim_calc_elastic(n, ptr(self.IP_kernel), ptr(self.IP_dNx), ptr(self.dof), ptr(RF), ptr(VF), None, stream_ptr()), "calc_elastic")
+        check(lib().pn_sim_calc_elastic(n, ptr(self.IP_kernel), ptr(self.IP_dNx), ptr(self.dof), ptr(RF), ptr(VF), None, self.svd_sweeps, stream_ptr()),
+              "calc_elastic")
         rhs = torch.empty_like(self.dof)
         check(lib().pn_sim_collect_rhs(self.n_k, float(self.dx), ptr(self.kernel_bg), ptr(self.kernel_cnt), ptr(self.buffer), ptr(self.IP_mu),
                                        ptr(self.IP_lam), ptr(self.IP_dNx), ptr(RF), ptr(VF), ptr(rhs), stream_ptr()), "collect_rhs")
@@ -329,13 +330,14 @@ class Simulator:
 
     def enable_persistent(self):
         """Switch to the persistent substep (a harness calls this for a GPU that only simulates: the owner rank of a frame-parallel job with a
-        dedicated simulator).  PN_SIM_COOP=0 vetoes it; scenes that do not fit keep the launch form.  Returns whether it is on."""
-        if os.environ.get("PN_SIM_COOP", "") == "0":
+        dedicated simulator).  PN_SIM_COOP=0 vetoes it, so does svd='mcadams' (the persistent form has the default decomposition only); scenes that
+        do not fit keep the launch form.  Returns whether it is on."""
+        if os.environ.get("PN_SIM_COOP", "") == "0" or self.svd_sweeps:
             return False
         self.persistent = True
-        if getattr(self, "_prepared", False) and self._coop is None:
+        if self._prepared and self._coop is None:
             self._prepare_persistent()
-        return self.persistent and (self._coop is not None or not getattr(self, "_prepared", False))
+        return self.persistent and (self._coop is not None or not self._prepared)
 
     def persistent_timed_out(self):
         """True if a persistent substep gave up waiting at a device-wide barrier (its workgroups could not all become resident): results invalid."""
@@ -346,7 +348,6 @@ class Simulator:
         return flag.value != 0
 
     def stepforward(self):  # solver.py:595-602
-        check(lib().pn_sim_set_svd(self.svd_sweeps), "sim_set_svd")   # process-global in the library: every enqueue names its own choice
         if not self._prepared:
             check(lib().pn_sim_prepare(self.n_k, self.n_IP, ptr(self.kernel_bg), ptr(self.kernel_cnt), ptr(self._work), stream_ptr()), "sim_prepare")
             self._prepared = True
@@ -360,18 +361,18 @@ class Simulator:
                                                 ptr(self._work), ptr(buf), n_wg, plan, stream_ptr()), "stepforward_coop")
             return
         if self.cell_form and self._cells is not None and int(self.iters) >= 1:
-            if self._cells_work is None:   # precompute() ran again since initialize(): the layout is new, so is its work area
-                self._prepare_cells()
+            if self._cells_work is None:
+                raise RuntimeError("Simulator: the cell form's work area is missing (precompute() prepares it on a GPU device)")
             c = self._cells
             check(lib().pn_sim_stepforward_cells(self.n_k, c["n_chunks"], int(self.iters), float(self.dt), float(self.dx), ptr(c["tab"]), ptr(c["dNx"]),
                                                  ptr(c["mu"]), ptr(c["lam"]), ptr(c["kp_bg"]), ptr(c["kp_pos"]), ptr(self.Ainv), ptr(self.Mmat),
                                                  ptr(self.dof_rest), ptr(self.rhs_rest), ptr(self.rhs_gravity), ptr(self.dof_f), ptr(self.dof), ptr(self.dof_vel),
-                                                 ptr(self._cells_work), stream_ptr()), "stepforward_cells")
+                                                 ptr(self._cells_work), self.svd_sweeps, stream_ptr()), "stepforward_cells")
             return
         check(lib().pn_sim_stepforward(self.n_k, self.n_IP, int(self.iters), float(self.dt), float(self.dx), ptr(self.IP_kernel), ptr(self.kernel_bg),
                                        ptr(self.kernel_cnt), ptr(self.buffer), ptr(self.IP_mu), ptr(self.IP_lam), ptr(self.IP_dNx), ptr(self.dNx_csr), ptr(self.csr_pos), ptr(self.Ainv),
                                        ptr(self.Mmat), ptr(self.dof_rest), ptr(self.rhs_rest), ptr(self.rhs_gravity), ptr(self.dof_f), ptr(self.dof),
-                                       ptr(self.dof_vel), ptr(self._work), 1, stream_ptr()), "stepforward")
+                                       ptr(self.dof_vel), ptr(self._work), 1, self.svd_sweeps, stream_ptr()), "stepforward")
 
     step = stepforward  # BASELINE.json's name for the same entry point
 

@@ -12,7 +12,7 @@ def rot(axis, ang):
 def adversarial_F(seed=0):
     """[n, 3, 3] deformation gradients that decide R = U V^T (cuda_utils.py:107-116): random, inverted (det < 0), repeated singular values,
     pure rotations, +-identity, rank 2 / 1 / 0, 1e-12- and 1e+8-scaled, nearly repeated.  The set of
-    test_gpu_edges.py::test_calc_elastic_on_adversarial_deformation_gradients, in its order."""
+    test_gpu_edges.py::test_calc_elastic_jacobi_argument_on_adversarial_deformation_gradients, in its order."""
     rng = np.random.default_rng(seed)
     Q1, Q2 = rot([1, 2, 3], 0.7), rot([-2, 1, 0.5], 2.1)
     mats = [np.eye(3) + 0.3 * rng.standard_normal((3, 3)) for _ in range(300)]

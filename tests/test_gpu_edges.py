@@ -361,8 +361,8 @@ def test_composite_with_chunk_loops_equals_one_workgroup_per_chunk():
     assert res[0] == res[1] and int(res[0][1]) > 5000 and res[0][3] == "0"
 
 
-def test_calc_elastic_on_adversarial_deformation_gradients():
-    """pn_sim_calc_elastic (k_elastic: cyclic-Jacobi SVD with rcp/rsq + Newton instead of IEEE div/sqrt, det-+1 contract of wp.svd3, volume
+def test_calc_elastic_jacobi_argument_on_adversarial_deformation_gradients():
+    """pn_sim_calc_elastic with mcadams_sweeps = 0 (k_elastic: cyclic-Jacobi SVD with rcp/rsq + Newton instead of IEEE div/sqrt, det-+1 contract of wp.svd3, volume
     projection) on deformation gradients that decide R = U V^T: inverted (det < 0), rank 2, rank 1, zero, repeated singular values, pure
     rotations, 1e-12- and 1e+8-scaled, plus random ones — against the CPU oracle (1e-9) and, where F is non-singular, against the polar
     rotation of numpy.linalg.svd (cuda_utils.py:83-121)."""
@@ -398,7 +398,7 @@ def test_calc_elastic_on_adversarial_deformation_gradients():
     RF_ref, VF_ref, FF_ref = oracle.calc_elastic(topo, dNx, dof.reshape(-1, 3))
     RF, VF, FF = (torch.empty(n, 3, 3, dtype=torch.float64, device=DEV) for _ in range(3))
     topo_d, dNx_d, dof_d = T(topo), T(dNx), T(dof.reshape(-1))   # kept alive until the kernel has run
-    check(lib().pn_sim_calc_elastic(n, ptr(topo_d), ptr(dNx_d), ptr(dof_d), ptr(RF), ptr(VF), ptr(FF), stream_ptr()), "calc_elastic")
+    check(lib().pn_sim_calc_elastic(n, ptr(topo_d), ptr(dNx_d), ptr(dof_d), ptr(RF), ptr(VF), ptr(FF), 0, stream_ptr()), "calc_elastic")
     torch.cuda.synchronize()
     RF, VF, FF = RF.cpu().numpy(), VF.cpu().numpy(), FF.cpu().numpy()
     # R is finite for every input; V F is finite exactly where the oracle's (= the reference's arithmetic) is: for F = 0 volume_invariant_project

@@ -7,7 +7,7 @@ nothing to assume: every SVD with sigma >= 0 gives the same polar rotation R and
 in the singular values).  So the tests here run the trajectories of BASELINE.json's three single-GPU configurations — with the forces bench.py
 applies — and check that det F stays positive at every integration point of every substep: on these workloads the assumed branch is dormant
 and the simulator's results do not depend on it.  (A scene that does invert elements is covered by
-test_gpu_edges.py::test_calc_elastic_on_adversarial_deformation_gradients against the oracle's contract only.)
+test_gpu_edges.py::test_calc_elastic_jacobi_argument_on_adversarial_deformation_gradients against the oracle's contract only.)
 
 Also here: the arrival counters of the chunked right-hand-side gather are cyclic (round-3 advisor finding)."""
 import numpy as np
@@ -72,9 +72,10 @@ def _sim_with(cloud, opt, svd, form):
 
 
 @pytest.mark.parametrize("name", list(CONFIGS))
-def test_svd_gap_on_the_baseline_trajectories(name):
+def test_svd_gap_per_simulator_on_the_baseline_trajectories(name):
     """wp.svd3 (cuda_utils.py:107) is third-party and absent; the repository holds the contract (converged Jacobi: the oracle's default and the HIP
-    kernels' default) and the published algorithm (McAdams et al.: the oracle's svd3_mcadams and the kernels' PN_SIM_SVD=mcadams mode).  On each
+    kernels' default) and the published algorithm (McAdams et al.: the oracle's svd3_mcadams and the kernels' PN_SIM_SVD=mcadams mode); six simulators
+    with their own svd= choice, which each passes to its launches as mcadams_sweeps.  On each
     BASELINE trajectory (configs[1], [1] forced, [2], [4]), 10 substeps of 10 local/global iterations from the same GPU-initialised state:
       * HIP default vs oracle(converged), HIP mcadams:8 vs oracle(mcadams 8), HIP mcadams:4 vs oracle(mcadams 4): <= 1e-9 of the displacements —
         each kernel mode IS its restatement (cell form and CSR form);
@@ -113,12 +114,28 @@ def test_svd_gap_on_the_baseline_trajectories(name):
     g4 = np.abs(ref["mcadams:4"] - ref["jacobi"]).max() / disp
     print(f"{name}: n_IP {s0.n_IP}: converged vs mcadams 8 sweeps {g8:.2e}, vs 4 sweeps {g4:.2e} (of max |displacement| after 10 substeps)")
     assert g8 < 1e-5 and g4 < 1e-2
-    from pienerf_amd._lib import lib
-    lib().pn_sim_set_svd(0)
 
 
-def test_mcadams_mode_on_the_adversarial_set():
-    """pn_sim_calc_elastic under pn_sim_set_svd(8) / (4) against the oracle's svd3_mcadams with the same sweep count on the adversarial
+def test_two_svd_choices_stepped_alternately_on_one_stream(small_cloud, small_opt):
+    """A jacobi and a mcadams:4 simulator stepped in turn on one stream end bit-identical to each one stepped alone, in the cell and the CSR form:
+    every launch carries its own decomposition (the mcadams_sweeps argument), nothing is left in the library for the next launch to read."""
+    def run(svds, form, steps=6):
+        sims = [_sim_with(small_cloud, small_opt, svd, form) for svd in svds]
+        for _ in range(steps):
+            for s in sims:
+                s.stepforward()
+        torch.cuda.synchronize()
+        return [(s.dof.clone(), s.dof_vel.clone()) for s in sims]
+    for form in ("cells", "csr"):
+        both = run(("jacobi", "mcadams:4"), form)
+        alone = run(("jacobi",), form) + run(("mcadams:4",), form)
+        for (d, v), (d1, v1) in zip(both, alone):
+            assert torch.equal(d, d1) and torch.equal(v, v1), form
+        assert not torch.equal(both[0][0], both[1][0]), form   # the two choices do give different trajectories
+
+
+def test_mcadams_sweeps_argument_on_the_adversarial_set():
+    """pn_sim_calc_elastic with mcadams_sweeps 8 / 4 against the oracle's svd3_mcadams with the same sweep count on the adversarial
     deformation gradients (inverted, rank-deficient, repeated singular values, 1e-12- and 1e+8-scaled): the same algorithm, so the same R and
     U diag(sigma') V^T to rounding wherever they are finite — including where the algorithm and the contract part ways."""
     import oracle
@@ -130,34 +147,30 @@ def test_mcadams_mode_on_the_adversarial_set():
     T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
     topo_d, dNx_d, dof_d = T(topo), T(dNx), T(dof.reshape(-1))
     scale = np.maximum(1.0, np.abs(Fs).max(axis=(1, 2)))[:, None, None]
-    try:
-        for sweeps in (8, 4):
-            with oracle.svd_mode("mcadams", sweeps=sweeps):
-                R0, V0, F0 = oracle.calc_elastic(topo, dNx, dof)
-            check(lib().pn_sim_set_svd(sweeps), "set_svd")
-            RF, VF, FF = (torch.empty(n, 3, 3, dtype=torch.float64, device=DEV) for _ in range(3))
-            check(lib().pn_sim_calc_elastic(n, ptr(topo_d), ptr(dNx_d), ptr(dof_d), ptr(RF), ptr(VF), ptr(FF), stream_ptr()), "calc_elastic")
-            torch.cuda.synchronize()
-            RF, VF, FF = RF.cpu().numpy(), VF.cpu().numpy(), FF.cpu().numpy()
-            fin = np.isfinite(V0).all(axis=(1, 2)) & np.isfinite(R0).all(axis=(1, 2))
-            assert np.array_equal(np.isfinite(VF).all(axis=(1, 2)) & np.isfinite(RF).all(axis=(1, 2)), fin)
-            # Where F^T F has (nearly) repeated eigenvalues — pure rotations, +-identity, repeated or vanishing singular values — the test
-            # gamma sh^2 < ch^2 compares rounding noise, so the two builds may take the fallback rotation a different number of times; each
-            # fallback leaves the quaternion 5e-10 short of unit length (the 10-digit constants), so R agrees to that noise level only (1e-7),
-            # or — rank-deficient F — is not determined at all.  Everywhere else the two are the same arithmetic: 1e-9.
-            eR = np.abs(RF - R0).max(axis=(1, 2))
-            vs = np.maximum(1.0, np.abs(V0).max(axis=(1, 2)))
-            eV = np.abs(VF - V0).max(axis=(1, 2)) / np.where(np.isfinite(vs), vs, 1.0)
-            agree = fin & (eR < 1e-9)
-            ok = fin & well_conditioned(Fs)
-            print(f"mcadams {sweeps} sweeps on the adversarial set: {agree.sum()} of {fin.sum()} finite cases agree to 1e-9 (max |V - V_oracle| there "
-                  f"{eV[agree].max():.2e}); the others: {np.flatnonzero(fin & ~agree).tolist()}, of them determined: "
-                  f"{np.flatnonzero(ok & ~agree).tolist()} with |R - R_oracle| <= {eR[ok & ~agree].max() if (ok & ~agree).any() else 0.0:.2e}")
-            assert agree[:380].all() and eV[agree].max() < 1e-9            # the 380 random / inverted gradients: the same arithmetic
-            assert agree.sum() >= fin.sum() - 12 and eR[ok].max() < 1e-6    # the degenerate ones: the constants' noise level where R is determined
-            assert np.abs((FF - F0) / scale)[agree].max() < 1e-9 and np.abs((FF - F0) / scale)[fin].max() < 1e-6
-    finally:
-        lib().pn_sim_set_svd(0)
+    for sweeps in (8, 4):
+        with oracle.svd_mode("mcadams", sweeps=sweeps):
+            R0, V0, F0 = oracle.calc_elastic(topo, dNx, dof)
+        RF, VF, FF = (torch.empty(n, 3, 3, dtype=torch.float64, device=DEV) for _ in range(3))
+        check(lib().pn_sim_calc_elastic(n, ptr(topo_d), ptr(dNx_d), ptr(dof_d), ptr(RF), ptr(VF), ptr(FF), sweeps, stream_ptr()), "calc_elastic")
+        torch.cuda.synchronize()
+        RF, VF, FF = RF.cpu().numpy(), VF.cpu().numpy(), FF.cpu().numpy()
+        fin = np.isfinite(V0).all(axis=(1, 2)) & np.isfinite(R0).all(axis=(1, 2))
+        assert np.array_equal(np.isfinite(VF).all(axis=(1, 2)) & np.isfinite(RF).all(axis=(1, 2)), fin)
+        # Where F^T F has (nearly) repeated eigenvalues — pure rotations, +-identity, repeated or vanishing singular values — the test
+        # gamma sh^2 < ch^2 compares rounding noise, so the two builds may take the fallback rotation a different number of times; each
+        # fallback leaves the quaternion 5e-10 short of unit length (the 10-digit constants), so R agrees to that noise level only (1e-7),
+        # or — rank-deficient F — is not determined at all.  Everywhere else the two are the same arithmetic: 1e-9.
+        eR = np.abs(RF - R0).max(axis=(1, 2))
+        vs = np.maximum(1.0, np.abs(V0).max(axis=(1, 2)))
+        eV = np.abs(VF - V0).max(axis=(1, 2)) / np.where(np.isfinite(vs), vs, 1.0)
+        agree = fin & (eR < 1e-9)
+        ok = fin & well_conditioned(Fs)
+        print(f"mcadams {sweeps} sweeps on the adversarial set: {agree.sum()} of {fin.sum()} finite cases agree to 1e-9 (max |V - V_oracle| there "
+              f"{eV[agree].max():.2e}); the others: {np.flatnonzero(fin & ~agree).tolist()}, of them determined: "
+              f"{np.flatnonzero(ok & ~agree).tolist()} with |R - R_oracle| <= {eR[ok & ~agree].max() if (ok & ~agree).any() else 0.0:.2e}")
+        assert agree[:380].all() and eV[agree].max() < 1e-9            # the 380 random / inverted gradients: the same arithmetic
+        assert agree.sum() >= fin.sum() - 12 and eR[ok].max() < 1e-6    # the degenerate ones: the constants' noise level where R is determined
+        assert np.abs((FF - F0) / scale)[agree].max() < 1e-9 and np.abs((FF - F0) / scale)[fin].max() < 1e-6
 
 
 def test_configs0_as_baseline_states_it_on_the_gpu():

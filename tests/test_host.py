@@ -31,6 +31,31 @@ def test_library_exports_every_declared_symbol():
     assert h.pn_compact_scratch_ints(1000) >= 4 and h.pn_sim_work_doubles(10, 20) >= 10 * 30 * 4
 
 
+def test_svd_choice_is_an_argument_not_a_library_global():
+    """The decomposition is chosen per launch (mcadams_sweeps of pn_sim_calc_elastic / pn_sim_stepforward / pn_sim_stepforward_cells): the library
+    exports no process-global setter, and a sweep count outside 0..64 is refused before anything is enqueued."""
+    import ctypes
+    from pienerf_amd import _lib
+    so = ctypes.CDLL(_lib.LIB_PATH)
+    for name in ("pn_sim_set_svd", "pn_sim_get_svd"):
+        assert not hasattr(so, name), name
+        assert name not in _declared_symbols() and name not in _lib.SIGNATURES
+    h, dummy = _lib.lib(), ctypes.c_void_p(16)
+    for sweeps in (-1, 65):
+        assert h.pn_sim_calc_elastic(1, dummy, dummy, dummy, dummy, dummy, None, sweeps, None) == 1   # PN_ERR_ARG
+
+
+def test_simulator_lifecycle_before_initialize():
+    """reset_warm_start() before initialize() does nothing; enable_persistent() refuses svd='mcadams' (the persistent form has the default
+    decomposition only) and leaves the form as it was."""
+    from pienerf_amd.simulator.solver import Simulator
+    s = Simulator(device="cpu", svd="mcadams:4", persistent=False)
+    s.reset_warm_start()
+    assert s.enable_persistent() is False and s.persistent is False
+    d = Simulator(device="cpu", persistent=False)
+    d.reset_warm_start()
+
+
 def test_no_mfma_overwrites_its_own_sources(tmp_path):
     """hipcc (ROCm 7.2) does not mark the destination of v_mfma_f32_32x32x16_bf16 early-clobber; when a source dies in the first MFMA
     of an accumulator chain the allocator may hand its registers to the destination (pn_nerf_forward.hip, split_mac orders the

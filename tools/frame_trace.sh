@@ -9,7 +9,6 @@ rows=sorted(csv.DictReader(open(f[0])), key=lambda r:int(r['Start_Timestamp']))
 # the last frame starts at the last k_frame_tables
 idx=[i for i,r in enumerate(rows) if 'k_frame_tables' in r['Kernel_Name']]
 i0=idx[-1]
-# include the simulator kernels enqueued around it: take everything from the last k_step_begin before i0, if close
 t0=int(rows[i0]['Start_Timestamp']); prev_end=t0
 print('   start     dur     gap  kernel')
 tot=0

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """stepforward(sim_iters) of the chair simulator alone on the GPU: ms per substep from a captured graph (what the frame pipeline replays).
-    python tools/time_sim.py [--iters 10] [--reps 300]        (environment knobs of csrc/pn_sim.hip select experimental variants)"""
+    python tools/time_sim.py [--iters 10] [--reps 300]        (PN_SIM_FORM=csr: the CSR launch form instead of the cell form)"""
 import argparse
 import os
 import sys
