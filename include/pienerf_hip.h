@@ -493,6 +493,29 @@ int pn_sim_prepare(int n_k, int n_IP, const int* csr_bg, const int* csr_cnt, dou
 int pn_sim_update_force(int n_k, int vid, const double* f3_host, double dx, const int* topo, const double* rho, const double* Nx, double* dof_f,
                         void* stream);
 
+/* The GUI's mouse drag on the device (nerf/gui.py:556-586, :833-841, :647-657; csrc/pn_drag.hip).  The state lives in device memory, so a substep
+ * captured into a HIP graph follows the cursor without a recapture.  Layout (the host reads `vid` back after a pick): */
+typedef struct pn_drag_state {
+    int vid;           /* picked integration point */
+    int active;        /* 0: no force (dof_f = 0, clear_force) */
+    double target[3];  /* cursor point in world space */
+    double scale;      /* the GUI's force_scale */
+} pn_drag_state;
+uint64_t pn_sim_drag_bytes(void);        /* sizeof(pn_drag_state) */
+uint64_t pn_sim_drag_work_doubles(void); /* doubles of pn_sim_drag_unproject's `work` */
+/* dof_f [10 n_k,3] = update_force(vid, f) with f = scale 1e5 (target - pos[vid]), pos[vid] = get_IP_info()'s fp32 position of the CURRENT dof, |f|
+ * clamped to 5e5; all zero when !active.  One launch, enqueued in front of a substep on its stream. */
+int pn_sim_drag_force(int n_k, int n_IP, const void* drag, const double* dof, double dx, const int* topo, const double* rho, const double* Nx,
+                      double* dof_f, void* stream);
+/* Writes the fields given: vid >= 0 (< n_IP), active >= 0 (0 or 1), scale > 0, target3_host != NULL; the others keep their value. */
+int pn_sim_drag_set(void* drag, int n_IP, int vid, int active, double scale, const double* target3_host, void* stream);
+/* screen_to_world: target = pose16 (c2w, row-major) @ [(x-cx)/fx d, (y-cy)/fy d, d, 1] with d = depth0[int(x) * 2 int(cy) + int(y)] (the reference's
+ * depth.reshape(2cx, 2cy)[x, y]; W H must equal 2 int(cx) * 2 int(cy)), d == 0 -> the mean of the nonzero depths (fixed-order sum).  intr4 =
+ * (fx, fy, cx, cy).  n_IP > 0 (a click): also vid = argmin |ip_pos [n_IP,3] fp32 - target|^2 (lowest index on ties), active = 1.  Two launches;
+ * `work`: pn_sim_drag_work_doubles() doubles.  A pixel outside [0, 2cx) x [0, 2cy) is PN_ERR_ARG. */
+int pn_sim_drag_unproject(const float* depth0, int W, int H, double x, double y, const double* intr4, const double* pose16, const float* ip_pos,
+                          int n_IP, void* drag, double* work, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -104,6 +104,11 @@ SIGNATURES = {
     "pn_sim_coop_clocks": (i32, [P, C.POINTER(u64)]),
     "pn_sim_stepforward_coop": (i32, [i32, i32, i32, f64, f64, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, i32, C.POINTER(i32), P]),
     "pn_sim_update_force": (i32, [i32, i32, P, f64, P, P, P, P, P]),
+    "pn_sim_drag_bytes": (u64, []),
+    "pn_sim_drag_work_doubles": (u64, []),
+    "pn_sim_drag_force": (i32, [i32, i32, P, P, f64, P, P, P, P, P]),
+    "pn_sim_drag_set": (i32, [P, i32, i32, i32, f64, P, P]),
+    "pn_sim_drag_unproject": (i32, [P, i32, i32, f64, f64, P, P, P, i32, P, P, P]),
 }
 
 _lib = None

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "pn_common.h"
+#include "pn_sim_ip.h"
 
 // The substep is a chain of ~30 short dependent launches that runs concurrently with the render kernels of other frames
 // (harness.capture_pipelined): its waves ask the SIMD arbiter for the highest user priority so the chain's latency does not
@@ -386,14 +387,7 @@ __global__ void __launch_bounds__(256) k_update_F(int n_IP, const int* __restric
         if (row == 0) S = Nx + ((size_t)v * 8 + i) * 10;
         else if (row < 4) S = dNx + (((size_t)v * 8 + i) * 3 + (row - 1)) * 10;
         else S = ddNx + (((size_t)v * 8 + i) * 9 + (row - 4)) * 10;
-        const double* __restrict__ d = dof + (size_t)kid * 30;
-#pragma unroll
-        for (int x = 0; x < 10; x++) {
-            const double s = S[x];
-            a0 += d[x * 3] * s;
-            a1 += d[x * 3 + 1] * s;
-            a2 += d[x * 3 + 2] * s;
-        }
+        pn_ip_row_acc(dof + (size_t)kid * 30, S, a0, a1, a2);
     }
     if (row == 0) {
         pos[v * 3] = (float)a0; pos[v * 3 + 1] = (float)a1; pos[v * 3 + 2] = (float)a2;
@@ -1752,16 +1746,7 @@ __global__ void __launch_bounds__(256) k_update_force(int n30, int vid, double f
                                                       const double* __restrict__ rho, const double* __restrict__ Nx, double* __restrict__ dof_f) {
     const int o = threadIdx.x + blockIdx.x * blockDim.x;
     if (o >= n30) return;
-    double v = 0.0;
-    if (vid >= 0) {
-        const int row = o / 3, r = o - row * 3, kid = row / 10, j = row - kid * 10;
-        const double f = r == 0 ? fx : (r == 1 ? fy : fz);
-        const double m = rho[vid] * dx3;
-        // an IP's 8 neighbour kernels are distinct, so at most one slot matches; summing keeps the reference's `+=` semantics otherwise
-        for (int i = 0; i < 8; i++)
-            if (topo[vid * 8 + i] == kid) v += m * Nx[((size_t)vid * 8 + i) * 10 + j] * f;
-    }
-    dof_f[o] = v;
+    dof_f[o] = vid >= 0 ? pn_force_entry(o, vid, fx, fy, fz, dx3, topo, rho, Nx) : 0.0;
 }
 
 extern "C" int pn_sim_update_force(int n_k, int vid, const double* f3_host, double dx, const int* topo, const double* rho, const double* Nx,

@@ -238,6 +238,9 @@ class FramePipeline:
         res = b.result(ws)
         if self.on_retire is not None:
             self.on_retire(f, res)
+            fence = getattr(b, "consumer_fence", None)   # the consumer's device work on its own stream must precede the workspace's next render
+            if fence is not None:
+                fence(ws)
         return f, res
 
     def step(self, pose=None):

@@ -128,6 +128,8 @@ class SimRenderHarness:
                 out = m.render_deformed(rays["rays_o"], rays["rays_d"], staged=True, bg_color=None, perturb=False, **kw)
             else:
                 out = m.rund_cuda_ops(rays["rays_o"], rays["rays_d"], bg_color=None, perturb=False, **kw)
+        if self.sim.drag_enabled:   # what drag() / move() unproject against (only then: without the drag nothing else is kept alive)
+            self._drag_frame = ("eager", out["depth_0"].reshape(H, W), m.p_def, pose, intrinsics)
         return {"image": out["image"].reshape(-1, H, W, 3), "depth": out["depth"].reshape(-1, H, W), "depth_0": out["depth_0"].reshape(-1, H, W),
                 "rays_o": rays["rays_o"], "rays_d": rays["rays_d"]}
 
@@ -161,6 +163,7 @@ class SimRenderHarness:
         if not hasattr(self, "_sim_stream"):
             self._sim_stream = torch.cuda.Stream(self.device)
         self._graph_pose = torch.from_numpy(np.asarray(self.pose, np.float32)).unsqueeze(0).to(self.device)
+        self._graph_pose_host = self.pose
         keep = (self.sim.dof.clone(), self.sim.dof_vel.clone())
         warm = torch.cuda.Stream(self.device)
         warm.wait_stream(torch.cuda.current_stream(self.device))
@@ -177,6 +180,7 @@ class SimRenderHarness:
         self.sim.reset_warm_start()       # ... and its SVD warm start: a replay from here has the bits of a simulator that never warmed up
         self._graph_trips = n_trips
         self._graph_done = None
+        self._graph_drag = self.sim.drag_enabled   # the substep's k_drag_force launch is in the graph or it is not
         self._graph_form_epoch = self._net_form_epoch()
         return self
 
@@ -206,6 +210,13 @@ class SimRenderHarness:
         self._graph_done = torch.cuda.Event()
         self._graph_done.record(torch.cuda.current_stream(self.device))
         self.frame += 1
+        if pose is not None:
+            self._graph_pose_host = pose
+        if self._graph_drag:
+            g = self._graph_out
+            self._drag_frame = ("graph", g["depth_0"][0], g["_ip"][0], self._graph_pose_host, self.intrinsics)
+        else:
+            self._drag_frame = ("graph",)
         return self._graph_out
 
     def finish_graph_frame(self):
@@ -286,6 +297,8 @@ class SimRenderHarness:
                                    sim_owner=sim_owner, dedicated_sim=dedicated_sim, copy_out=copy_out, on_retire=on_retire,
                                    force_collectives=bool(_force_collectives) and on, sim_on_lanes=sim_on_lanes)
         self.sim.force_hooks = (self._pipe.before_force, self._pipe.after_force) if self._pipe.sim_on_lanes else None
+        self._pipe_drag = self.sim.drag_enabled
+        self._drag_frame = ("pipelined",)
         self._pipe_backend = be
         self._pipe_form_epoch = self._net_form_epoch()
         self.model._in_flight = lambda pipe=self._pipe: sum(f is not None for f in pipe.pending)  # weight refreshes need a drained pipeline (network._net_handle)
@@ -423,6 +436,58 @@ class SimRenderHarness:
     def finish_staged(self):
         return self.drain_pipeline()
 
+    # ------------------------------------------------------------------ the GUI's mouse drag (gui.py:556-586, :833-841)
+    def enable_drag(self, scale=None):
+        """Simulator.enable_drag: every substep from now on gets the GUI's spring force toward the cursor, computed on the device from the state that
+        substep starts from.  Call it BEFORE capture() / capture_pipelined(): a graph captured without it has no drag launch and refuses drag()."""
+        self.sim.enable_drag(scale)
+        return self
+
+    def _drag_check(self):
+        if not self.sim.drag_enabled:
+            raise RuntimeError("drag: call enable_drag() first (before capture() / capture_pipelined())")
+        mode = getattr(self, "_drag_frame", None)
+        if mode is None:
+            raise RuntimeError("drag: no frame has been rendered yet (the cursor is unprojected against the last frame's depth_0)")
+        if mode[0] == "graph" and not getattr(self, "_graph_drag", False):
+            raise RuntimeError("drag: the step graph was captured before enable_drag(), its substep ignores the drag state: capture() again")
+        if mode[0] == "pipelined" and not getattr(self, "_pipe_drag", False):
+            raise RuntimeError("drag: the pipeline was captured before enable_drag(), its substep ignores the drag state: capture_pipelined() again")
+        return mode
+
+    def _drag_inputs(self, depth0, ip_pos, pick):
+        mode = self._drag_check()
+        if mode[0] == "pipelined":
+            # the caller hands in the last RETIRED frame's depth_0: the cursor is then unprojected against an image `lanes * depth` frames older than
+            # the state the next substep reads — inherent to the pipeline.  The pick searches the IPs of the simulator's newest state.
+            if depth0 is None:
+                raise ValueError("drag in the pipelined form: pass depth0, the depth_0 of the last frame step_pipelined() returned")
+            depth0 = torch.as_tensor(depth0).to(self.device, torch.float32).contiguous()
+            if pick and ip_pos is None:
+                with self.sim._on_force_stream():
+                    ip_pos = self.sim.get_IP_info()[0]
+            return depth0, ip_pos, self.pose, self.intrinsics
+        if mode[0] == "graph":
+            self._check_previous_graph_frame()   # a frame left with rays alive is finished before its depth_0 is read
+        return (mode[1] if depth0 is None else depth0), (mode[2] if ip_pos is None else ip_pos), mode[3], mode[4]
+
+    def drag(self, x, y, depth0=None, ip_pos=None):
+        """A ctrl-click at image pixel (x, y) (gui.py:833-841): picks the integration point nearest to the unprojected cursor among the IP positions
+        the last returned frame was rendered from, against that frame's depth_0 and camera; the drag then acts from the next substep on.  Returns
+        the picked IP.  (x, y) are image pixels: a window's own offsets, as dearpygui's +20 title bar (gui.py:809-812), are the caller's."""
+        d, ip, pose, intr = self._drag_inputs(depth0, ip_pos, True)
+        return self.sim.drag_pick(d, x, y, pose, intr, ip)
+
+    def move(self, x, y, depth0=None):
+        """The cursor moved to (x, y): the spring's target is unprojected against the last returned frame's depth_0 (gui.py:578).  No host read."""
+        d, _, pose, intr = self._drag_inputs(depth0, None, False)
+        self.sim.drag_to(d, x, y, pose, intr)
+
+    def release(self):
+        """Nothing picked any more: the following substeps run without force (the GUI's clear_force)."""
+        self._drag_check()
+        self.sim.release()
+
     def to_host(self, out):
         """The reference's device->host boundary (trainer.py:589-592)."""
         return {k: out[k][0].detach().cpu().numpy() for k in ("image", "depth", "depth_0")}
@@ -508,6 +573,7 @@ class _HipBackend:
         sim.force_stream = self._streams["sim"]   # a force change is enqueued between two substeps of the simulator stream
         self.snap = {}
         n_ws, n_IP = lanes * depth, sim.n_IP
+        self.consumer_done = [None] * n_ws   # per workspace: the event behind what on_retire enqueued on its stream (consumer_fence)
         kw = dict(h.render_kwargs(), async_trips=n_trips)
         kw.update(render_kw or {})  # options of THIS pipeline's renders (capture_staged: ray_batch)
         # several frames in flight: the first trip's march pass in its throughput form (pn_render_opts.throughput: one lane per ray, no speculative
@@ -668,8 +734,18 @@ class _HipBackend:
         with torch.cuda.stream(s.s):
             dist.broadcast(self._snap(slot), src=self.src, group=self.group)
 
+    def consumer_fence(self, ws):
+        """After on_retire(frame, result): whatever the consumer enqueued on its current stream (a copy of the device tensors) is ordered before
+        the workspace's next render overwrites them."""
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.h.device))
+        self.consumer_done[ws] = ev
+
     def render(self, s, frame, ws, slot, pose):
         with torch.cuda.stream(s.s):
+            if self.consumer_done[ws] is not None:
+                s.s.wait_event(self.consumer_done[ws])
+                self.consumer_done[ws] = None
             # the camera of this frame (trainer.py:541): the given pose, else the harness's current one.  Every workspace keeps its own device
             # copy (the graph reads it), so it is uploaded whenever it differs from what THIS workspace last rendered — staged in pinned memory,
             # in stream order before the graph reads it

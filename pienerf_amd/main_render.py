@@ -3,7 +3,7 @@ does for one frame — load a point cloud and a checkpoint, step the simulator, 
 deformed point cloud and the per-frame IP state the reference's ``main_render.py`` reads back from ``./debug``).
 
     python -m pienerf_amd.main_render --frames 30 --out output_img/chair [--ply model/chair_0.ply] [--ckpt ws/checkpoints/ngp_ep0300.pth]
-           [--W 800 --H 800] [--radius 5 --azimuth 0 --elevation 0 --fovy 50] [--force fx fy fz] [--save_ply] [--save_ip_state]
+           [--W 800 --H 800] [--radius 5 --azimuth 0 --elevation 0 --fovy 50] [--force fx fy fz | --drag X0 Y0 X1 Y1] [--save_ply] [--save_ip_state]
 
 Without --ply / --ckpt the synthetic chair of pienerf_amd.scene is used (there are no assets on the GPU box).
 Reference: main_gui.py:20-66 (model + simulator construction), nerf/gui.py:556-645 (test_step: IP info -> substep -> render),
@@ -41,8 +41,23 @@ def run(args):
     if args.force is not None:
         vid = args.force_vid if args.force_vid >= 0 else h.sim.IP_pos.shape[0] // 2
         h.sim.update_force(vid, torch.tensor(args.force, dtype=torch.float64, device=h.device))
+    if args.drag is not None:  # a scripted mouse drag (gui.py:556-586, :833-841): pick at (X0, Y0) on frame 0, the cursor moves linearly to (X1, Y1)
+        if args.force is not None:
+            raise SystemExit("--drag and --force both set the force: choose one")
+        h.enable_drag(args.drag_scale)
+        h.step(pose=pose, simulate=False)   # the frame the first pick is unprojected against (not written)
     written, t0 = [], time.time()
     for f in range(args.frames):
+        if args.drag is not None:
+            x0, y0, x1, y1 = args.drag
+            t = f / max(args.frames - 1, 1)
+            x, y = x0 + t * (x1 - x0), y0 + t * (y1 - y0)
+            if f == 0:
+                vid = h.drag(x, y)
+                if not args.quiet:
+                    print(f"drag: picked IP {vid} at pixel ({x:.1f}, {y:.1f})")
+            else:
+                h.move(x, y)
         out = h.to_host(h.step(pose=pose, collect_stats=True))
         path = os.path.join(args.out, f"img_{f}.png")
         io.save_image(out["image"], path, args.W, args.H)
@@ -84,6 +99,9 @@ def parser():
     ap.add_argument("--num_seek_IP", type=int, default=3)
     ap.add_argument("--force", type=float, nargs=3, default=None, help="constant force on one IP (gui.py drag), e.g. 300 100 -200")
     ap.add_argument("--force_vid", type=int, default=-1)
+    ap.add_argument("--drag", type=float, nargs=4, default=None, metavar=("X0", "Y0", "X1", "Y1"),
+                    help="scripted mouse drag: pick the IP under pixel (X0, Y0) on frame 0, move the cursor linearly to (X1, Y1) over the frames")
+    ap.add_argument("--drag_scale", type=float, default=1.0, help="the GUI's force_scale of the drag (mouse wheel, gui.py:857-865)")
     ap.add_argument("--save_ply", action="store_true")
     ap.add_argument("--save_ip_state", action="store_true")
     ap.add_argument("--device", default="cuda:0")

@@ -8,6 +8,7 @@ Kept: constructor arguments, ``InitializeFromPly``, ``get_IP_info`` (fp32, permu
     ([10 n_k]^2 instead of [30 n_k]^2, solver.py:493-496,532-538) — same products, 9x fewer bytes;
   * importing this module does not call ``torch.set_default_device("cuda")`` (func_utils.py:6).
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -31,6 +32,23 @@ class _null_ctx:
 
 
 CELL_CHUNK_IPS = 32   # points per chunk of the substep's cell form = pn_sim_cells_chunk_ips() (csrc/pn_sim.hip: PN_CELL_IPS), checked in _prepare_cells
+
+
+DRAG_SCALE_MIN, DRAG_SCALE_MAX = 1e-3, 5e1   # gui.py:865
+
+
+def wheel_force_scale(scale, delta):
+    """The GUI's mouse-wheel rule for the drag's force scale (gui.py:857-865): +-0.5 per notch above 1, +-0.1 at or below, clamped to [1e-3, 50]."""
+    scale = float(scale)
+    scale += delta * 0.5 if scale > 1.0 else delta * 0.1
+    return max(DRAG_SCALE_MIN, min(scale, DRAG_SCALE_MAX))
+
+
+def _check_scale(s):
+    s = float(s)
+    if not (np.isfinite(s) and s > 0.0):
+        raise ValueError(f"drag force scale must be a positive finite number, got {s!r}")
+    return s
 
 
 class Simulator:
@@ -76,6 +94,10 @@ class Simulator:
         # BETWEEN two substeps instead of racing with one
         self.force_stream = None
         self.force_hooks = None   # (before, after): a pipeline whose substeps do not run on force_stream orders the change between two of them (frames.FramePipeline)
+        # the GUI's mouse drag on the device (enable_drag): a pn_drag_state in device memory, read by a k_drag_force launch in front of every substep
+        self.drag_enabled = False
+        self.drag_force_scale = 1.0
+        self._drag = self._drag_work = None
 
     # ------------------------------------------------------------------ IO (solver.py:109-137)
     def InitializeFromPly(self, path):
@@ -105,6 +127,8 @@ class Simulator:
         self._work = torch.empty(int(lib().pn_sim_work_doubles(self.n_k, self.n_IP)), dtype=torchfloat, device=self.device)
         self._prepared = False
         self.rhs_rest = (self.build_rhs() + self._matvec(self.Mmat, self.dof)).contiguous()   # solver.py:314
+        if self.drag_enabled and self.device.type == "cuda":
+            self._alloc_drag()
 
     def precompute(self):
         """Everything of initialize() that is tensor bookkeeping / torch.linalg (device-agnostic), and on a GPU the cell form's work area for the
@@ -348,6 +372,9 @@ class Simulator:
         return flag.value != 0
 
     def stepforward(self):  # solver.py:595-602
+        if self.drag_enabled:   # the spring force of THIS substep's state (gui.py:556-586), on the substep's stream, captured with it into graphs
+            check(lib().pn_sim_drag_force(self.n_k, self.n_IP, ptr(self._drag), ptr(self.dof), float(self.dx), ptr(self.IP_kernel), ptr(self.IP_rho),
+                                          ptr(self.IP_Nx), ptr(self.dof_f), stream_ptr()), "sim_drag_force")
         if not self._prepared:
             check(lib().pn_sim_prepare(self.n_k, self.n_IP, ptr(self.kernel_bg), ptr(self.kernel_cnt), ptr(self._work), stream_ptr()), "sim_prepare")
             self._prepared = True
@@ -376,15 +403,16 @@ class Simulator:
 
     step = stepforward  # BASELINE.json's name for the same entry point
 
-    def _force_launch(self, vid, f3):
+    @contextlib.contextmanager
+    def _on_force_stream(self):
+        """Runs the enclosed launches on `force_stream` (or the current stream), ordered BETWEEN two substeps."""
         st = self.force_stream
         if st is not None:  # ordered between two substeps of the simulator's own stream, after whatever the caller has enqueued so far
             st.wait_stream(torch.cuda.current_stream(self.device))
             if self.force_hooks:
                 self.force_hooks[0]()
         with torch.cuda.stream(st) if st is not None else _null_ctx():
-            check(lib().pn_sim_update_force(self.n_k, int(vid), f3.ctypes.data if f3 is not None else None, float(self.dx), ptr(self.IP_kernel),
-                                            ptr(self.IP_rho), ptr(self.IP_Nx), ptr(self.dof_f), stream_ptr()), "update_force")
+            yield
         if st is not None:
             # ... and before whatever the caller enqueues next on ITS stream: a substep launched there (sim.stepforward(), a whole-step graph) must
             # not read dof_f while the kernel above is still writing it
@@ -394,15 +422,111 @@ class Simulator:
             if self.force_hooks:
                 self.force_hooks[1]()
 
+    def _force_launch(self, vid, f3):
+        if self.drag_enabled:
+            raise RuntimeError("Simulator: the drag state owns dof_f while drag is enabled (enable_drag); use drag_to / release instead of update_force / clear_force")
+        with self._on_force_stream():
+            check(lib().pn_sim_update_force(self.n_k, int(vid), f3.ctypes.data if f3 is not None else None, float(self.dx), ptr(self.IP_kernel),
+                                            ptr(self.IP_rho), ptr(self.IP_Nx), ptr(self.dof_f), stream_ptr()), "update_force")
+
     def update_force(self, vid, f):  # solver.py:578-588
         """dof_f = the pick force `f` on IP `vid`, written whole by one launch on `force_stream` (or the current stream): it acts from the
         next substep enqueued after this call."""
+        if self.drag_enabled:
+            self._force_launch(vid, None)   # raises
         f3 = np.ascontiguousarray(f.detach().cpu().numpy() if torch.is_tensor(f) else f, dtype=np.float64)
         assert 0 <= int(vid) < self.n_IP and f3.shape == (3,)
         self._force_launch(vid, f3)
 
     def clear_force(self):  # solver.py:590-593
         self._force_launch(-1, None)
+
+    # ------------------------------------------------------------------ the GUI's mouse drag on the device (gui.py:556-586, :833-841, :857-865)
+    def enable_drag(self, scale=None):
+        """From now on every stepforward() first writes dof_f with the GUI's spring force from the drag state (csrc/pn_drag.hip: k_drag_force):
+        f = scale 1e5 (target - p0), |f| <= 5e5, p0 = the picked IP's get_IP_info() position of the state that substep starts from; all zero until
+        drag_pick().  The state lives in device memory, so substeps captured into graphs after this call follow drag_to() without a recapture.
+        While drag is enabled the drag state owns dof_f: update_force / clear_force raise.  May be called before initialize()."""
+        if scale is not None:
+            self.drag_force_scale = _check_scale(scale)
+        if not self.drag_enabled:
+            self.drag_enabled = True
+            if self.dof is not None and self.device.type == "cuda":
+                self._alloc_drag()
+        return self
+
+    def _alloc_drag(self):
+        nb = int(lib().pn_sim_drag_bytes())
+        if nb != 40:
+            raise RuntimeError(f"libpienerf_hip.so's pn_drag_state has {nb} bytes, solver.py allocates 40")
+        self._drag = torch.zeros(5, dtype=torchfloat, device=self.device)          # vid, active = 0; target = 0
+        self._drag_work = torch.zeros(int(lib().pn_sim_drag_work_doubles()), dtype=torchfloat, device=self.device)
+        check(lib().pn_sim_drag_set(ptr(self._drag), self.n_IP, -1, -1, float(self.drag_force_scale), None, stream_ptr()), "sim_drag_set")
+        self.dof_f.zero_()
+
+    def _drag_state(self):
+        if not self.drag_enabled:
+            raise RuntimeError("Simulator: drag is not enabled (call enable_drag() first)")
+        if self._drag is None:
+            raise RuntimeError("Simulator: the drag state lives on a GPU: initialize the simulator on a cuda device first")
+        return self._drag
+
+    def _unproject(self, depth0, x, y, pose, intrinsics, ip_pos):
+        drag = self._drag_state()
+        d = depth0.reshape(depth0.shape[-2], depth0.shape[-1]) if depth0.dim() >= 2 else depth0
+        if d.dtype != torch.float32 or not d.is_cuda or not d.is_contiguous():
+            raise ValueError("drag: depth0 must be a contiguous fp32 [H, W] tensor on the GPU (a frame's depth_0)")
+        H, W = d.shape
+        intr = np.ascontiguousarray(np.asarray(intrinsics, np.float64).reshape(4))
+        pose16 = np.ascontiguousarray(np.asarray(pose, np.float64).reshape(-1)[-16:])
+        n = 0
+        if ip_pos is not None:
+            if ip_pos.dtype != torch.float32 or not ip_pos.is_cuda or tuple(ip_pos.shape) != (self.n_IP, 3) or not ip_pos.is_contiguous():
+                raise ValueError("drag_pick: ip_pos must be the contiguous fp32 [n_IP, 3] IP positions of a frame, on the GPU")
+            n = self.n_IP
+        with self._on_force_stream():
+            check(lib().pn_sim_drag_unproject(ptr(d), W, H, float(x), float(y), intr.ctypes.data, pose16.ctypes.data, ptr(ip_pos), n, ptr(drag),
+                                              ptr(self._drag_work), stream_ptr()), "sim_drag_unproject")
+
+    def drag_pick(self, depth0, x, y, pose, intrinsics, ip_pos):
+        """A ctrl-click at pixel (x, y) (gui.py:833-841): target = screen_to_world(x, y) against `depth0` ([H, W] fp32, the last frame's depth_0),
+        the drag acts on the IP of `ip_pos` ([n_IP, 3] fp32, the IP positions that frame was rendered from) nearest to it.  Returns that IP's index:
+        the drag's one read back to the host.  (x, y) are image pixels; a window's own offsets (dearpygui's +20 title bar, gui.py:809-812) are the
+        caller's business."""
+        self._unproject(depth0, x, y, pose, intrinsics, ip_pos)
+        st = self.force_stream if self.force_stream is not None else torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(st):
+            vid = self._drag[:1].view(torch.int32)[0].item()
+        return int(vid)
+
+    def drag_to(self, depth0, x, y, pose, intrinsics):
+        """The cursor moved to pixel (x, y): target = screen_to_world(x, y) against `depth0` (gui.py:647-657).  No host read."""
+        self._unproject(depth0, x, y, pose, intrinsics, None)
+
+    def drag_scale(self, s):
+        """Sets the GUI's force_scale (f = s 1e5 (target - p0))."""
+        self.drag_force_scale = _check_scale(s)
+        if self._drag is not None:
+            with self._on_force_stream():
+                check(lib().pn_sim_drag_set(ptr(self._drag), self.n_IP, -1, -1, float(self.drag_force_scale), None, stream_ptr()), "sim_drag_set")
+        return self.drag_force_scale
+
+    def drag_wheel(self, delta):
+        """The mouse wheel's rule (gui.py:857-865) applied to the force scale; returns the new scale."""
+        return self.drag_scale(wheel_force_scale(self.drag_force_scale, delta))
+
+    def drag_hold(self, vid, target):
+        """Drags IP `vid` toward the world point `target` (no unprojection): scripted drags and tests."""
+        t = np.ascontiguousarray(np.asarray(target, np.float64).reshape(3))
+        drag = self._drag_state()
+        with self._on_force_stream():
+            check(lib().pn_sim_drag_set(ptr(drag), self.n_IP, int(vid), 1, 0.0, t.ctypes.data, stream_ptr()), "sim_drag_set")
+
+    def release(self):
+        """Nothing picked (right click / Q, gui.py:821-826,843-849): every following substep gets dof_f = 0, as after clear_force()."""
+        drag = self._drag_state()
+        with self._on_force_stream():
+            check(lib().pn_sim_drag_set(ptr(drag), self.n_IP, -1, 0, 0.0, None, stream_ptr()), "sim_drag_set")
 
     def update_pos(self):  # solver.py:604-617 (update_pos_kernel) — only used by OutputToPly
         d = self.dof.view(self.n_k, 10, 3)[self.pts_kernel.long()]

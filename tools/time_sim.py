@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """stepforward(sim_iters) of the chair simulator alone on the GPU: ms per substep from a captured graph (what the frame pipeline replays).
-    python tools/time_sim.py [--iters 10] [--reps 300]        (PN_SIM_FORM=csr: the CSR launch form instead of the cell form)"""
+    python tools/time_sim.py [--iters 10] [--reps 300] [--drag]        (PN_SIM_FORM=csr: the CSR launch form instead of the cell form)"""
 import argparse
 import os
 import sys
@@ -15,12 +15,16 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--iters", type=int, default=10)
 ap.add_argument("--reps", type=int, default=300)
 ap.add_argument("--persistent", action="store_true", help="the local/global iterations as one cooperative kernel (pn_sim_stepforward_coop)")
+ap.add_argument("--drag", action="store_true", help="drag enabled (Simulator.enable_drag): k_drag_force in front of every substep, IP n_IP/2 held")
 args = ap.parse_args()
 o = scene.default_opt()
 c = scene.make_chair_points(hgs=o["hash_grid_size"])
 sim = Simulator(dt=o["sim_dt"], iters=args.iters, bbox=torch.tensor([2.0 * o["bound"]] * 3), dx=o["sim_dx"], stiff=o["sim_stiff"], base=torch.tensor([-o["bound"]] * 3),
                 device="cuda:0", persistent=args.persistent)
 sim.InitializeFromArrays(c["pos"], c["mass"], c["mu"], c["lam"], c["pin"])
+if args.drag:
+    sim.enable_drag()
+    sim.drag_hold(sim.n_IP // 2, [0.2, 0.3, -0.1])
 for _ in range(20):
     sim.stepforward()
 torch.cuda.synchronize()
@@ -52,5 +56,5 @@ if args.persistent and sim._coop is not None and int(os.environ.get("PN_SIM_COOP
         print(f"   {nme:40s} {tk * 0.01 / launches / args.iters:7.2f} us per iteration")
 if args.persistent:
     print("persistent:", sim._coop is not None and (sim._coop[1], list(sim._coop[2])), "timed out:", sim.persistent_timed_out())
-print(f"stepforward({args.iters}): {ms:.4f} ms per substep, {ms / max(args.iters, 1) * 1e3:.1f} us per local/global iteration; n_k {sim.n_k}, n_IP {sim.n_IP}; max |dof - rest| {disp:.4e}",
+print(f"stepforward({args.iters}){' with drag' if args.drag else ''}: {ms:.4f} ms per substep, {ms / max(args.iters, 1) * 1e3:.1f} us per local/global iteration; n_k {sim.n_k}, n_IP {sim.n_IP}; max |dof - rest| {disp:.4e}",
       {k: v for k, v in os.environ.items() if k.startswith("PN_SIM")})
