@@ -553,7 +553,7 @@ extern "C" void pn_net_destroy(pn_net* n) {
 
 // Workgroup = 8 waves sharing ONE 61 KB LDS weight image, one workgroup per CU = 2 waves per SIMD (rounds 1-2: two 4-wave workgroups per CU with an
 // image each — the same waves with 122 KB of LDS, which kept the other render lanes' march workgroups (48 KB) off the CU; round 3: in-loop launches
-// 0.280 -> 0.265 ms per frame, pipelined step unchanged.  16 waves per CU (-DPN_BF_WAVES=8 with PN_NERF_BLOCKS=512) are faster alone, 0.249 ms, and cost
+// 0.280 -> 0.265 ms per frame, pipelined step unchanged.  16 waves per CU (512 such workgroups) are faster alone, 0.249 ms, and cost
 // the pipelined step 5 %: the march kernels want the wave slots).
 // MINW = waves per SIMD the register allocator must leave room for; LU = how many hash levels' gathers are in flight per lane.
 #ifndef PN_BF_WAVES
@@ -691,7 +691,7 @@ int pn_nerf_forward_launch(const pn_net* net, const float* xyzs, const float* di
     const uint32_t tiles = pn_div_up(M_max, 32);
     if (half) {
         PN_REQUIRE(net->emb_half);  // pn_net_enable_half first
-        static const uint32_t max_blocks_h = pn_env_u32("PN_NERF_BLOCKS_H", 1024);  // 4 workgroups per CU
+        const uint32_t max_blocks_h = 1024;  // 4 workgroups per CU
         uint32_t blocks = std::min(pn_div_up(tiles, PN_H_WAVES), max_blocks_h);
         if (blocks_cap) blocks = std::min(blocks, blocks_cap);
         k_nerf_forward_h<4, 4><<<blocks, PN_H_WAVES * 64, PN_NET_HALF_BYTES + 16 * sizeof(PnFusedLevel), stream>>>((const PnFusedLevel*)net->fused_levels, (const uint32_t*)net->emb_half,
@@ -700,7 +700,7 @@ int pn_nerf_forward_launch(const pn_net* net, const float* xyzs, const float* di
         PN_LAUNCH_CHECK();
         return PN_OK;
     }
-    static const uint32_t max_blocks = pn_env_u32("PN_NERF_BLOCKS", 2048 / PN_BF_WAVES);  // 8 waves per CU x 256 CUs; waves stride over tiles
+    const uint32_t max_blocks = 2048 / PN_BF_WAVES;  // 8 waves per CU x 256 CUs; waves stride over tiles
     uint32_t blocks = pn_div_up(tiles, PN_BF_WAVES);
     if (blocks > max_blocks) blocks = max_blocks;
     if (blocks_cap) blocks = std::min(blocks, blocks_cap);

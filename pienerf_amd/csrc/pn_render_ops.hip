@@ -338,12 +338,8 @@ __global__ void __launch_bounds__(1024) k_scan_tile_apply(int n_grid_max, const 
 // exclusive scan cnt -> bgn, cursor over up to n_grid_max cells (the live count may come from device memory)
 static void launch_cell_scan(int n_grid_max, const int* n_grid_dev, const int* cnt, int* bgn, int* cursor, hipStream_t st) {
     const int tiles = (int)pn_div_up(n_grid_max, 4096);
-    // Measured on the trex option set (300 k cells): the tiled form (three launches) shortens a single frame (1.04 vs 1.15 ms eager) and — since the
-    // pipeline's rate is its lanes' chain latency (round 4: frames per second = lanes / latency of a lane's launches) — the pipelined step as well:
-    // 1 464 -> 1 535 steps/s (profiles/r04_trex_scan.txt).  (Round 1 measured the opposite, 1.30 vs 1.13 ms per step, when a lane's chain was ~45
-    // launches and the one long workgroup hid behind the other lanes.)  PN_TILED_SCAN=0: the one-workgroup scan.
-    static const bool tiled = pn_env_u32("PN_TILED_SCAN", 1) != 0;
-    if (!tiled || tiles <= 16 || tiles > 1024) {  // small grids: one workgroup is faster than three launches
+    // the tiled form (three launches) over the one-workgroup scan on the trex option set (300 k cells): 1 464 -> 1 535 steps/s (profiles/r04_trex_scan.txt)
+    if (tiles <= 16 || tiles > 1024) {  // small grids: one workgroup is faster than three launches
         k_pig_scan<<<1, 1024, 0, st>>>(n_grid_max, n_grid_dev, cnt, bgn, cursor);
         return;
     }
@@ -650,40 +646,28 @@ static_assert(sizeof(TailEntry) == 64, "four 16-byte parts");
 // G = 1: ONE lane per ray, 256 rays per block — every evaluated point is a visited one (no speculation: a quarter of the VALU work per visited point of
 // the windows, whose lanes evaluate 4.6 elements per voxel hop), at one visited point per round (the windows: ~14).  The throughput form of a frame's
 // first trip (pn_render_opts.throughput): the wave-per-ray tail pass that the pipelined step is bound by only gets the rays that outlast the budget.
-// WPB != 4 (G = 1 only): the PACKED form of the one-lane pass — WPB waves (12 KB of staging each, dynamic LDS) in ONE workgroup that takes a whole CU, the
-// 64-ray chunks dealt per WAVE.  The first trip's ~1 100 busy waves then sit on ~90 CUs, three per SIMD, instead of one workgroup of 4 on every CU of
-// the chip: a march wave is a chain of dependent instructions that leaves its SIMD idle four cycles in five, so three of them interleave almost for
-// free — and the other frames' fused launches (one 157-KB workgroup per CU, which no CU with a march workgroup on it can take) find the rest of the
-// chip free instead of waiting for the march to end.
-#ifndef PN_MARCH_PACK_WAVES
-#define PN_MARCH_PACK_WAVES 12
-#endif
-template <int K, bool MULTI, int G, int WPB = 4>
-__global__ void __launch_bounds__(WPB * 64, WPB == 4 ? PN_MARCH_WAVES : 1) k_march(pnm::MarchParams a, pnm2::March2Tables tb, MarchIO io) {
+template <int K, bool MULTI, int G>
+__global__ void __launch_bounds__(256, PN_MARCH_WAVES) k_march(pnm::MarchParams a, pnm2::March2Tables tb, MarchIO io) {
     uint32_t n_alive = io.n_alive, n_step_trip = io.n_step;
     bool dense = false;
     if (io.trip) { n_alive = (uint32_t)io.trip->n_alive; n_step_trip = (uint32_t)io.trip->n_step; dense = trip_is_dense(io.trip); }
     static_assert(G == 8 || G == 1, "lanes per ray");
-    constexpr bool WAVE_DEAL = WPB != 4;
-    static_assert(!WAVE_DEAL || G == 1, "the packed form is the one-lane pass");
-    constexpr uint32_t RB = WAVE_DEAL ? 64u : 256u / G;  // rays per chunk: a workgroup's (a wave's) share per step of its loop
+    constexpr uint32_t RB = 256u / G;  // rays per chunk: a workgroup's share per step of its loop
     const int lane = threadIdx.x & 63, sub = lane & (G - 1), gbase = lane & ~(G - 1);
     const int budget = io.tail ? io.max_rounds : 0x7fffffff;
-    __shared__ float4 stage_mem[WAVE_DEAL ? 1 : 4][WAVE_DEAL ? 1 : PN_STAGE_CAP];
-    extern __shared__ __attribute__((aligned(16))) float4 stage_dyn[];   // WAVE_DEAL: WPB x PN_STAGE_CAP entries
-    float4* stage = WAVE_DEAL ? stage_dyn + (size_t)(threadIdx.x >> 6) * PN_STAGE_CAP : stage_mem[WAVE_DEAL ? 0 : (threadIdx.x >> 6)];
+    __shared__ float4 stage_mem[4][PN_STAGE_CAP];
+    float4* stage = stage_mem[threadIdx.x >> 6];
     // 32-ray chunks are dealt round-robin to a bounded grid: in frame mode the alive count is only known on the device, and a
     // grid sized for all N rays would push ~20 000 mostly empty workgroups through the dispatcher on every trip.  With an active list
     // (trip 0) workgroup b walks segment b % PN_SEGS of it; either way `seg` names the segment this workgroup's own appends go to.
-    // (WAVE_DEAL: read "wave" for "workgroup".)
-    const uint32_t unit = WAVE_DEAL ? blockIdx.x * WPB + (threadIdx.x >> 6) : blockIdx.x, n_units = WAVE_DEAL ? gridDim.x * WPB : gridDim.x;
+    const uint32_t unit = blockIdx.x, n_units = gridDim.x;
     const uint32_t act_seg = unit % PN_SEGS;
     const uint32_t n_work = io.active ? (uint32_t)seg_count(io.active_counts, (int)act_seg) : n_alive;
     const uint32_t k0 = io.active ? unit / PN_SEGS : unit, kstep = io.active ? (uint32_t)seg_workers((int)n_units, (int)act_seg) : n_units;
     PN_PHASE_DECL(pk);
     for (uint32_t chunk = k0; chunk * RB < n_work; chunk += kstep) {
         const uint32_t seg = io.active ? act_seg : chunk % PN_SEGS;
-        const uint32_t i_work = chunk * RB + (WAVE_DEAL ? (uint32_t)lane : threadIdx.x / G);
+        const uint32_t i_work = chunk * RB + threadIdx.x / G;
         const uint32_t n = io.active ? (i_work < n_work ? (uint32_t)io.active[(size_t)act_seg * io.active_seg_cap + i_work] : 0xffffffffu) : i_work;
         uint32_t emitted = 0;
         bool deferred = false, have = false;
@@ -826,23 +810,7 @@ __global__ void __launch_bounds__(256, PN_MARCH_WAVES) k_march_tail(pnm::MarchPa
 
 template <int K, bool MULTI>
 static void launch_march_km(uint32_t blocks, uint32_t tail_blocks, hipStream_t st, const pnm::MarchParams& a, const pnm2::March2Tables& tb, const MarchIO& io) {
-    // PN_MARCH_PACK=1 (experiments): the one-lane pass packed into whole-CU workgroups (see k_march, WPB).  Bit-identical, and measured neutral in the
-    // pipeline on all three configurations (profiles/r05/march_pack_ab.txt), so the default stays four waves per workgroup all over the chip
-    static const bool pack = pn_env_u32("PN_MARCH_PACK", 0) != 0;
-    if (io.lane_per_ray && pack) {
-        constexpr int W = PN_MARCH_PACK_WAVES;
-        const size_t lds = (size_t)W * PN_STAGE_CAP * sizeof(float4);
-        static bool granted[PN_MAX_DEVICES] = {false};  // dynamic LDS above 64 KB is opted into per function and DEVICE
-        int dev_id = 0;
-        if (hipGetDevice(&dev_id) == hipSuccess && (dev_id < 0 || dev_id >= PN_MAX_DEVICES || !granted[dev_id])) {
-            (void)hipFuncSetAttribute((const void*)k_march<K, MULTI, 1, W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (dev_id >= 0 && dev_id < PN_MAX_DEVICES) granted[dev_id] = true;
-        }
-        // as many waves as the unpacked grid had (blocks x 4), at least PN_SEGS of them, at most one workgroup per CU: beyond that the waves loop
-        static const uint32_t pack_grid = pn_env_u32("PN_MARCH_PACK_GRID", 256);
-        const uint32_t wgs = std::max(std::min(pn_div_up(blocks * 4u, (uint32_t)W), pack_grid), pn_div_up((uint32_t)PN_SEGS, (uint32_t)W));
-        k_march<K, MULTI, 1, W><<<wgs, W * 64, lds, st>>>(a, tb, io);
-    } else if (io.lane_per_ray) k_march<K, MULTI, 1><<<blocks, 256, 0, st>>>(a, tb, io);
+    if (io.lane_per_ray) k_march<K, MULTI, 1><<<blocks, 256, 0, st>>>(a, tb, io);
     else k_march<K, MULTI, 8><<<blocks, 256, 0, st>>>(a, tb, io);
     if (io.tail) k_march_tail<K, MULTI><<<tail_blocks, 256, 0, st>>>(a, tb, io);
 }
@@ -856,15 +824,13 @@ static void launch_march(int K, uint32_t blocks, uint32_t tail_blocks, hipStream
     else { if (multi) launch_march_km<3, true>(blocks, tail_blocks, st, a, tb, io); else launch_march_km<3, false>(blocks, tail_blocks, st, a, tb, io); }
 }
 
-// Rounds of 8 sequence elements a ray gets in k_march before it is handed to the wave-per-ray tail pass (PN_TAIL_ROUNDS overrides).
-static int g_skip_dda_override = -1;    // pn_march_set_skip_dda (tests): 0 / 1 replace the default, -1: default (environment PN_SKIP_DDA)
+// Rounds of 8 sequence elements a ray gets in k_march before it is handed to the wave-per-ray tail pass.
+static int g_skip_dda_override = -1;    // pn_march_set_skip_dda (tests): 0 / 1 replace the default, -1: default (1)
 static int g_tail_rounds_override = 0;  // pn_march_set_tail_rounds (tests): > 0 replaces the default below
 // Defaults measured on the chair once the append lists were segmented (k_march + tail per trip, us): trip 0 (every ray looks for its first sample)
 // 232 / 201 / 210 / 211 for 1 / 2 / 3 / 4 rounds; later trips (alive rays, 8 samples each: most are done after one window) 70 / 76 / 78 / 79.
 static uint32_t march_tail_rounds(int trip = -1) {
-    static const uint32_t r = pn_env_u32("PN_TAIL_ROUNDS", 0);  // 0: per-trip defaults
     if (g_tail_rounds_override > 0) return (uint32_t)g_tail_rounds_override;
-    if (r) return r;
     return trip < 0 ? 4u : (trip == 0 ? 2u : 1u);
 }
 extern "C" int pn_march_set_skip_dda(int on) {
@@ -1430,15 +1396,14 @@ __global__ void __launch_bounds__(256) k_compact(const int* __restrict__ in, uin
 // behind its previous chunk to the prefix it already has: 512 words per chunk instead of all before it.
 // The tag makes last trip's words read as "not written yet"; the words are cleared once per frame (k_frame_prologue).  The workgroup of the
 // trip's LAST chunk has the grand total and runs trip_epilogue: every earlier chunk has published its count, i.e. finished its composites and
-// its per-group survivor atomics.  R = alive positions per thread (1; PN_CC_R0 = 2 / 4 for the frame's first trip are kept for experiments:
-// fewer chunks make the quadratic gather smaller, but the strided accesses of the composite cost more than that saves).
-template <int R>
+// its per-group survivor atomics.  R = 1 alive position per thread (2 / 4 on a frame's first trip: 21.4 / 27.9 us against 20.0).
 __global__ void __launch_bounds__(256) k_composite_compact(float T_thresh, const int* __restrict__ cur, int* __restrict__ nxt, float* rays_t,
                                                            const float* __restrict__ sigmas, const float* __restrict__ rgbs, const float* __restrict__ deltas,
                                                            float* weights_sum, float* depth, float* image, PnTrip* trip, PnTrip* next,
                                                            unsigned* words, uint32_t tag, uint32_t N_rays, uint32_t max_steps, int dense_trips,
                                                            int* seg_counters, int* tail_diag, const PnGroup* __restrict__ g_cur, PnGroup* __restrict__ g_next,
                                                            int* group_cnt, uint32_t group_rays, uint32_t n_groups, int* err_flag, uint32_t poll_cap) {
+    constexpr int R = 1;  // alive positions per thread (the loops over them stay: the compiled kernel is the one measured)
     __shared__ int s_wcnt[4], s_part[4];
     const uint32_t n_alive = (uint32_t)trip->n_alive, n_step_trip = (uint32_t)trip->n_step;
     const uint32_t CH = 256u * R;
@@ -2162,42 +2127,27 @@ static int render_impl(pn_frame* f, const pn_net* net, const pn_render_opts* o, 
     hipStream_t st = (hipStream_t)stream;
     const uint32_t nblk = pn_div_up(N, 256);
     // per-trip launches use bounded grids with round-robin chunk loops (the alive count lives on the device): 32 march blocks and
-    // 4 composite/compact blocks per CU (measured: 8192 march blocks is ~2 % faster than one block per 32 rays, 2048 is 6 % slower).
-    // PN_MARCH_GRID / PN_TRIP_GRID override for experiments.
-    static const uint32_t march_grid_cfg = pn_env_u32("PN_MARCH_GRID", 8192), trip_grid_cfg = pn_env_u32("PN_TRIP_GRID", 1024);
+    // 4 composite/compact blocks per CU (measured: 8192 march blocks is ~2 % faster than one block per 32 rays, 2048 is 6 % slower)
+    const uint32_t march_grid = 8192, trip_grid = std::min(nblk, 1024u);
     // trips after the first find at most N / 8 rays in the typical frame (n_step = 8) = N / 256 chunks of 32: a grid of that size (the chunk loop takes
     // care of frames with more) instead of 8192 mostly empty workgroups per launch — what an empty captured trip costs is dispatch
-    static const uint32_t march_grid_later_cfg = pn_env_u32("PN_MARCH_GRID_LATER", 0);
-    const uint32_t march_grid = march_grid_cfg, trip_grid = std::min(nblk, trip_grid_cfg);
-    const uint32_t march_grid_later = march_grid_later_cfg ? march_grid_later_cfg : std::max(std::min(pn_div_up(N, 256), march_grid_cfg), (uint32_t)PN_SEGS);
-    // PN_SKIP_LATE_START=1 (experiment, off by default): the skip pre-pass starts its hop chain at the last lattice element before the candidates'
-    // neighbourhood (pn_march_window.h).  Bit-identical in every march / frame test, but it only takes k_march_skip from 75 to 68 us on the chair (its
-    // bounding box lies almost entirely within two cells of the object: the leading walks are short already) — not worth a second code path by default.
-    // k_march_skip: DDA start + hop budget (pn_march_window.h: skip_empty_cells); PN_SKIP_DDA=0 walks hop by hop like rounds 1-2 (same results bit for bit)
-    static const int dda_env = [] { const char* v = getenv("PN_SKIP_DDA"); return (v && v[0] == '0') ? 0 : 1; }();
-    const int dda_start = g_skip_dda_override >= 0 ? g_skip_dda_override : dda_env;
-    static const uint32_t skip_hop_budget = pn_env_u32("PN_SKIP_HOPS", 8);
+    const uint32_t march_grid_later = std::max(std::min(pn_div_up(N, 256), march_grid), (uint32_t)PN_SEGS);
+    // k_march_skip: DDA start + hop budget (pn_march_window.h: skip_empty_cells); pn_march_set_skip_dda(0) walks hop by hop like rounds 1-2 (same results bit for bit)
+    const int dda_start = g_skip_dda_override >= 0 ? g_skip_dda_override : 1;
+    const uint32_t skip_hop_budget = 8;
     // a frame's first trip with ONE lane per ray in pass 1 (k_march<.., 1>) for this many rounds = visited points before a ray goes to the windows
-    static const uint32_t lpr_env = pn_env_u32("PN_MARCH_LPR", 0);
-    const uint32_t lpr_rounds = lpr_env ? lpr_env : (o->throughput > 0 ? (uint32_t)o->throughput : 0u);  // (PN_MARCH_LPR: experiments)
-    static const uint32_t lpr_trips_env = pn_env_u32("PN_MARCH_LPR_TRIPS", 0);  // experiments
-    const uint32_t lpr_trips = lpr_trips_env ? lpr_trips_env : (uint32_t)std::max(o->throughput_trips, 1);  // leading trips in that form
-    static const bool split_compact = pn_env_u32("PN_SPLIT_COMPACT", 0) != 0;  // experiments: composite and compaction as two launches (rounds 1-2)
-    static const uint32_t tail_grid_cfg = pn_env_u32("PN_TAIL_GRID", 1024);  // x4 waves, one unfinished ray per wave at a time
-    const uint32_t tail_grid = std::max(std::min(pn_div_up(N, 4), tail_grid_cfg), (uint32_t)PN_SEGS / 4);  // every tail segment needs a wave
+    const uint32_t lpr_rounds = o->throughput > 0 ? (uint32_t)o->throughput : 0u;
+    const uint32_t lpr_trips = (uint32_t)std::max(o->throughput_trips, 1);  // leading trips in that form
+    const uint32_t tail_grid = std::max(std::min(pn_div_up(N, 4), 1024u), (uint32_t)PN_SEGS / 4);  // x4 waves, one unfinished ray per wave at a time; every tail segment needs a wave
     // the skip pre-pass keeps the cells' emptiness bits in LDS when they fit (48 KB = 393 k cells)
     const size_t bit_words = (f->max_cells + 31) / 32;
     const bool short_rays = !is_static && !o->cut && bit_words * 8 <= 48 * 1024;  // both maps in LDS: rays end where their candidates end
     const int skip_bits_words = (short_rays || bit_words * 4 <= 48 * 1024) ? (int)bit_words : 0;
     // --cut: the region map for the skip pre-pass (MarchIO::grid_regions; pn_march_window.h: region_dda) where its assumptions hold: the top cascade level
-    // spans exactly +-bound (bound == 2^(C - 1)), regions are whole 64-byte lines of the bitfield and nest on every level, the map fits
-    static const bool grid_regions_off = pn_env_u32("PN_GRID_REGIONS_OFF", 0) != 0;   // A/B runs: same frames, bit for bit
-    // regions of 8^3 voxels (a 64-byte line of the bitfield).  PN_REGION_SIDE=4: 4^3-voxel regions (one 8-byte word) — measured on the trex option set alone:
-    // 232 against 177 us (hop by hop 285): the restart zone in front of an interesting region is longer than a 4-voxel region, so fewer runs qualify
-    static const uint32_t reg_side_env = pn_env_u32("PN_REGION_SIDE", 0);
-    const uint32_t reg_side = reg_side_env == 4 ? 4u : 8u;
-    const uint32_t reg_R = o->grid_size / reg_side;
-    const bool reg_ok = !is_static && o->cut && !grid_regions_off && dda_start && bitfield && o->grid_size % 32 == 0 && o->cascade >= 1 && o->cascade <= 3 &&
+    // spans exactly +-bound (bound == 2^(C - 1)), regions are whole 64-byte lines of the bitfield and nest on every level, the map fits.
+    // Regions of 8^3 voxels (a 64-byte line of the bitfield); 4^3-voxel regions measured 232 against 177 us on the trex option set (hop by hop 285)
+    const uint32_t reg_R = o->grid_size / 8;
+    const bool reg_ok = !is_static && o->cut && dda_start && bitfield && o->grid_size % 32 == 0 && o->cascade >= 1 && o->cascade <= 3 &&
                         o->bound == (float)(1u << (o->cascade - 1)) && (reg_R / 2) % (1u << (o->cascade - 1)) == 0 &&
                         (uint64_t)reg_R * reg_R * reg_R / 32 * o->cascade <= PN_GRID_REGION_WORDS && ((uintptr_t)bitfield & 15) == 0;
     const int grid_region_words_1 = reg_ok ? (int)((uint64_t)reg_R * reg_R * reg_R / 32) : 0;   // one map
@@ -2217,18 +2167,13 @@ static int render_impl(pn_frame* f, const pn_net* net, const pn_render_opts* o, 
     PN_REQUIRE(n_groups <= f->max_groups);
     PN_REQUIRE(!resume || group_rays == f->last_group_rays);
 
+    // where the fused launch applies (see fuse_from below)
+    const bool fused_ok = !is_static && !group_rays && o->fused_from >= 0 && o->max_steps <= 8u * PN_FUSED_MAX_TRIPS;
     // forms of the fused launch that take the frame from its first trip on (see the trip loop below) also write its epilogue: decided here, before the prologue
-    static const bool fused_env0 = [] { const char* v = getenv("PN_FUSED"); return !(v && v[0] == '0'); }();
-    static const int whole_env0 = [] { const char* v = getenv("PN_FUSED_WHOLE"); return !v ? -1 : (v[0] == '0' ? 0 : 1); }();
-    static const int fold_env0 = [] { const char* v = getenv("PN_FUSED_FOLD"); return !v ? -1 : (v[0] == '0' ? 0 : 1); }();
-    // Measured on the chair, alternating runs on one box (profiles/r04_early_finish_ab.txt): with the whole-frame launch (two lanes) 1 719 against 1 601
-    // steps/s; with the folded first trip (three lanes) 1 983 / 1 950 against 2 002 / 1 981 — there the dying rays' extra loads inside the launch cost what
-    // the launch off the chain saves.  So: the whole-frame form only.  PN_EARLY_FINISH=0: never; 2: with the folded first trip too (A/B)
-    static const uint32_t early_env = pn_env_u32("PN_EARLY_FINISH", 1);
-    const bool fused_ok0 = fused_env0 && !is_static && !group_rays && o->fused_from >= 0 && o->max_steps <= 8u * PN_FUSED_MAX_TRIPS;
-    const bool want_whole = fused_ok0 && (whole_env0 < 0 ? o->fused_whole != 0 : whole_env0 != 0) && o->fused_from == 0 && !resume;
-    const bool want_fold = fused_ok0 && !want_whole && (fold_env0 < 0 ? o->fused_fold != 0 : fold_env0 != 0) && o->fused_from <= 1 && !resume;
-    const bool early_finish = early_env != 0 && (want_whole || (want_fold && early_env >= 2));
+    const bool want_whole = fused_ok && o->fused_whole != 0 && o->fused_from == 0 && !resume;
+    const bool want_fold = fused_ok && !want_whole && o->fused_fold != 0 && o->fused_from <= 1 && !resume;
+    // the whole-frame form only (chair, profiles/r04_early_finish_ab.txt: 1 719 against 1 601 steps/s; with the folded first trip 1 983 / 1 950 against 2 002 / 1 981)
+    const bool early_finish = want_whole;
     const float* bbmin = f->dev->aabb;  // device addresses of struct members
     const float* bbmax = f->dev->aabb + 3;
     const int* res = f->dev->resolution;
@@ -2280,12 +2225,11 @@ static int render_impl(pn_frame* f, const pn_net* net, const pn_render_opts* o, 
     fp.weights_sum = weights_sum; fp.depth_0 = depth_0; fp.image = f->acc_image; fp.groups = group_rays ? f->groups : nullptr; fp.group_cnt = f->group_cnt;
     fp.group_rays = group_rays; fp.n_groups = n_groups; fp.chunk_words = f->chunk_counts;
     fp.early_finish = early_finish ? 1 : 0; fp.bg = o->bg_color; fp.image_out = image; fp.depth_out = depth;
-    {   // pn_render_opts.ray_tile_w; PN_RAY_TILE_OFF=1 keeps the row-major order (A/B runs: same frames, bit for bit)
-        static const bool tile_off = pn_env_u32("PN_RAY_TILE_OFF", 0) != 0;
-        static const uint32_t lw = std::min(pn_env_u32("PN_RAY_TILE_LOG2W", 4), 5u);  // experiments: 8 x 8 (3), 32 x 2 (5) pixel tiles
+    {   // pn_render_opts.ray_tile_w: 16 x 4 pixel tiles
+        const uint32_t lw = 4;
         const uint32_t tw = o->ray_tile_w > 0 ? (uint32_t)o->ray_tile_w : 0u;
         fp.tile_lw = lw;
-        fp.tile_w = (!tile_off && !is_static && !group_rays && tw && tw % (1u << lw) == 0 && N % ((64u >> lw) * tw) == 0) ? tw : 0u;
+        fp.tile_w = (!is_static && !group_rays && tw && tw % (1u << lw) == 0 && N % ((64u >> lw) * tw) == 0) ? tw : 0u;
     }
     // both cell maps of a workgroup in LDS while it builds its lists (up to 64 KB = 262 k cells; beyond that straight to global memory, where
     // the maps then span enough cache lines for the atomics not to queue)
@@ -2310,23 +2254,18 @@ static int render_impl(pn_frame* f, const pn_net* net, const pn_render_opts* o, 
     bool done = false;
     // The trips from `fuse_from` on as ONE launch (pn_trips_fused.h) where that form applies: a deformed frame with one trip schedule, max_steps within
     // the fused kernel's trip table.  pn_render_opts.fused_from: the first trip to run fused (0: 1 — right behind the frame's first trip; a scene whose
-    // later trips still have more than N / 8 rays alive — the trex option set's second — names a later one; < 0: never).  PN_FUSED=0 switches it off (A/B).
-    static const bool fused_env = [] { const char* v = getenv("PN_FUSED"); return !(v && v[0] == '0'); }();
-    static const uint32_t fused_grid_env = pn_env_u32("PN_FUSED_GRID", 0);
-    const bool fused_ok = fused_env && !is_static && !group_rays && o->fused_from >= 0 && o->max_steps <= 8u * PN_FUSED_MAX_TRIPS;
+    // later trips still have more than N / 8 rays alive — the trex option set's second — names a later one; < 0: never).
     const int fuse_from = fused_ok ? std::max(o->fused_from, 1) : PN_MAX_TRIPS + 1;
     int add_fused = 0;
     f->fused_first = -1;
     // ... and the WHOLE frame behind the skip pre-pass as one launch (pn_render_opts.fused_whole with fused_from == 0; pn_trips_fused.h, WHOLE): the launch checks on the
     // device that at most N / 8 rays have anything to march (then every trip after the first marches 8 samples per ray whatever the first one finds) and
     // does nothing otherwise — the blocking driver then goes on trip by trip as above, a fixed-trip render is left to pn_render_continue.
-    // PN_FUSED_WHOLE=0 / 1: never / wherever fused_from == 0 allows it (A/B runs).
-    static const uint32_t a_rounds_env = pn_env_u32("PN_FUSED_AROUNDS", 0);
     bool whole_try = want_whole && t == 0;
     // ... or the first trip's NETWORK, COMPOSITE and COMPACTION inside that launch (pn_render_opts.fused_fold with fused_from <= 1; pn_trips_fused.h, FOLD): the
     // march of the first trip stays what it is — skip pre-pass, one lane per ray / windows, tail pass, on every CU — and leaves the trip's segmented sample list;
     // the launch runs network tiles over it, composites, and takes the survivors on.  Four launches fewer on a frame's chain (k_list_pack, k_nerf_forward,
-    // k_composite, k_compact).  Applies when at most N / 8 rays found a sample (checked on the device); otherwise as with fused_whole.  PN_FUSED_FOLD=0 / 1: A/B.
+    // k_composite, k_compact).  Applies when at most N / 8 rays found a sample (checked on the device); otherwise as with fused_whole.
     bool fold_try = want_fold && t == 0;
     bool finished_in_launch = false;   // the frame's epilogue was written by the fused launch (early_finish)
     bool skip_done = resume && f->skip_done != 0;
@@ -2397,7 +2336,7 @@ static int render_impl(pn_frame* f, const pn_net* net, const pn_render_opts* o, 
             if (whole) {
                 fa.active = f->active_seg; fa.active_counts = seg_active; fa.active_seg_cap = (int)f->seg_cap; fa.t_resume = f->t_resume;
                 fa.blist = f->blist; fa.strag = f->strag; fa.blist_cap = f->blist_cap;
-                fa.a_rounds = a_rounds_env ? (int)a_rounds_env : 24;
+                fa.a_rounds = 24;
             }
             if (fold) {
                 fa.list_seg = f->list_seg; fa.samp_counts = seg_samp; fa.list_seg_cap = (int)f->seg_cap; fa.seg_tail = seg_tail; fa.seg_back = seg_back;
@@ -2416,7 +2355,7 @@ static int render_impl(pn_frame* f, const pn_net* net, const pn_render_opts* o, 
                 skip_done = true;
                 f->skip_done = 1;
             }
-            const uint32_t blocks = fused_grid_env ? std::min(fused_grid_env, f->fused_blocks) : (o->fused_grid > 0 ? std::min((uint32_t)o->fused_grid, f->fused_blocks) : f->fused_blocks);
+            const uint32_t blocks = o->fused_grid > 0 ? std::min((uint32_t)o->fused_grid, f->fused_blocks) : f->fused_blocks;
             rc = launch_trips_fused(o->num_seek_IP, o->max_iter_num > 1, o->fp16 ? 1 : (net->x_ok ? 2 : 0), whole ? 1 : (fold ? 2 : 0), blocks, st, mq, tb, fa);
             if (rc) return rc;
             if ((rc = time_mark(tb_idx, 1)) || (rc = time_mark(tb_idx, 2))) return rc;
@@ -2493,22 +2432,16 @@ static int render_impl(pn_frame* f, const pn_net* net, const pn_render_opts* o, 
             PnGroup* g_nxt = group_rays ? f->groups + (size_t)((t + 1) & 1) * f->max_groups : nullptr;
             const uint32_t pair_grid = margin ? std::min(trip_grid, 64u) : trip_grid;
             // a frame's first trip has every ray alive (2 500 chunks at 800x800): five rounds of the bounded fused kernel (31 us) cost more than the two
-            // launches (25 us), which poll nothing; PN_CC_TRIP0=1 keeps the fused form there
+            // launches (25 us), which poll nothing.  PN_CC_TRIP0=1 and PN_CC_GRID are test hooks (tests/test_gpu_edges.py): the fused form on trip 0, its grid
             static const bool cc_trip0 = pn_env_u32("PN_CC_TRIP0", 0) != 0;
-            if (!is_static && !split_compact && !margin && (t > 0 || cc_trip0)) {
+            if (!is_static && !margin && (t > 0 || cc_trip0)) {
                 // a bounded grid with chunk loops: all of a launch's workgroups can be resident at once, whatever order the XCDs start them in (see the kernel)
-#define PN_CC_LAUNCH(R_)                                                                                                                                   \
-    k_composite_compact<R_><<<std::min(cc_grid, pn_div_up(N, 256 * R_)), 256, 0, st>>>(o->T_thresh, cur, nxt, f->rays_t, f->sigmas, f->rgbs, f->deltas, weights_sum, depth_0,          \
-                                                                     f->acc_image, f->trips + t, f->trips + t + 1, (unsigned*)f->chunk_counts, (uint32_t)t + 1, N, \
-                                                                     o->max_steps, 1, f->seg_counters, f->tail_counts + t, g_cur, g_nxt, f->group_cnt, group_rays,  \
-                                                                     n_groups, err, cc_poll_cap)
                 static const uint32_t cc_grid = pn_env_u32("PN_CC_GRID", 512);
-                static const uint32_t cc_poll_cap = 1u << std::min(pn_env_u32("PN_CC_POLL_LOG2", 20), 30u);
-                static const uint32_t cc_r0 = pn_env_u32("PN_CC_R0", 1);  // alive positions per thread on a frame's first trip; measured 20.0 / 21.4 / 27.9 us for 1 / 2 / 4
-                if (t == 0 && cc_r0 >= 4) PN_CC_LAUNCH(4);
-                else if (t == 0 && cc_r0 == 2) PN_CC_LAUNCH(2);
-                else PN_CC_LAUNCH(1);
-#undef PN_CC_LAUNCH
+                const uint32_t cc_poll_cap = 1u << 20;
+                k_composite_compact<<<std::min(cc_grid, pn_div_up(N, 256)), 256, 0, st>>>(o->T_thresh, cur, nxt, f->rays_t, f->sigmas, f->rgbs, f->deltas, weights_sum,
+                                                                                     depth_0, f->acc_image, f->trips + t, f->trips + t + 1, (unsigned*)f->chunk_counts,
+                                                                                     (uint32_t)t + 1, N, o->max_steps, 1, f->seg_counters, f->tail_counts + t, g_cur,
+                                                                                     g_nxt, f->group_cnt, group_rays, n_groups, err, cc_poll_cap);
             } else {
             k_composite<<<pair_grid, 256, 0, st>>>(0, 0, o->T_thresh, cur, f->rays_t, f->sigmas, f->rgbs, f->deltas, weights_sum, depth_0, f->acc_image,
                                                    f->trips + t, f->chunk_counts, g_cur, group_rays, n_groups > 1 ? f->group_cnt : nullptr);

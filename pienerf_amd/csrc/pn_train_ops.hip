@@ -411,10 +411,8 @@ extern "C" int pn_march_rays_train(const float* rays_o, const float* rays_d, con
     PN_REQUIRE(rays_o && rays_d && grid && nears && fars && rays && counter && (M == 0 || (xyzs && dirs && deltas)));
     PN_REQUIRE(C >= 1 && C <= 8 && H > 0 && max_steps > 0);
     hipStream_t st = (hipStream_t)stream;
-    // wave per ray while that still fits the chip in a few rounds (training batches); lane per ray for whole images (PN_TRAIN_MARCH=lane|wave forces one)
-    static const char* form = getenv("PN_TRAIN_MARCH");
-    const bool wave = form ? strcmp(form, "wave") == 0 : N <= 131072;
-    if (wave) {
+    // wave per ray while that still fits the chip in a few rounds (training batches); lane per ray for whole images
+    if (N <= 131072) {
         k_train_count_w<<<pn_div_up(N, 4), 256, 0, st>>>(rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, nears, fars, rays, noises);
         k_train_scan<<<1, 1024, 0, st>>>(rays, N, counter);
         k_train_write_w<<<pn_div_up(N, 4), 256, 0, st>>>(rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, M, nears, fars, xyzs, dirs, deltas, rays,
@@ -433,8 +431,7 @@ extern "C" int pn_composite_rays_train_forward(const float* sigmas, const float*
                                                float T_thresh, float* weights_sum, float* depth, float* image, void* stream) {
     if (N == 0) return PN_OK;
     PN_REQUIRE(rays && weights_sum && depth && image && (M == 0 || (sigmas && rgbs && deltas)));
-    static const char* form = getenv("PN_TRAIN_COMPOSITE");  // lane | wave; default: wave per ray for training batches, lane per ray for whole images
-    if (form ? strcmp(form, "wave") == 0 : N <= 131072)
+    if (N <= 131072)  // wave per ray for training batches, lane per ray for whole images
         k_composite_train_w<false><<<pn_div_up(N, 4), 256, 0, (hipStream_t)stream>>>(nullptr, nullptr, sigmas, rgbs, deltas, rays, nullptr, nullptr, M, N, T_thresh,
                                                                                     weights_sum, depth, image, nullptr, nullptr);
     else
@@ -448,8 +445,7 @@ extern "C" int pn_composite_rays_train_backward(const float* grad_weights_sum, c
                                                 uint32_t N, float T_thresh, float* grad_sigmas, float* grad_rgbs, void* stream) {
     if (N == 0 || M == 0) return PN_OK;
     PN_REQUIRE(grad_weights_sum && grad_image && sigmas && rgbs && deltas && rays && weights_sum && image && grad_sigmas && grad_rgbs);
-    static const char* form = getenv("PN_TRAIN_COMPOSITE");
-    if (form ? strcmp(form, "wave") == 0 : N <= 131072)
+    if (N <= 131072)
         k_composite_train_w<true><<<pn_div_up(N, 4), 256, 0, (hipStream_t)stream>>>(grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N,
                                                                                    T_thresh, nullptr, nullptr, nullptr, grad_sigmas, grad_rgbs);
     else

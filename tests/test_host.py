@@ -325,3 +325,30 @@ def test_render_opts_mirror_follows_the_header():
     for (n, a), (_, b) in zip(got, want):
         assert C.sizeof(a) == C.sizeof(b) and getattr(a, "_type_", a) == getattr(b, "_type_", b), n
     assert C.sizeof(RenderOpts) == sum(C.sizeof(t) for _, t in want)
+
+
+def test_environment_reads_are_the_documented_allowlist():
+    """The package reads exactly these environment variables, and INTEGRATION.md ("Environment knobs") lists each: a retired experiment knob
+    cannot come back unnoticed.  Build-time -D variants (tools/build_variant.py) are not environment reads and are not collected here."""
+    allow = {
+        "PN_CC_GRID", "PN_CC_TRIP0",                          # test hooks of the fused composite + compaction (tests/test_gpu_edges.py)
+        "PN_NET_FORM",                                        # network form (tests/test_gpu_netform.py)
+        "PN_SIM_SVD", "PN_SIM_FORM", "PN_SIM_COOP", "PN_SIM_COOP_RESERVE", "PN_SIM_COOP_EU", "PN_SIM_COOP_DBG",
+        "PN_LIB_PATH",                                        # another build of the library (tools/build_variant.py)
+    }
+    pkg = os.path.join(ROOT, "pienerf_amd")
+    found = set()
+    for dirpath, dirnames, files in os.walk(pkg):
+        dirnames[:] = [d for d in dirnames if d not in ("lib", "__pycache__")]
+        for fn in files:
+            path = os.path.join(dirpath, fn)
+            if fn.endswith((".hip", ".h", ".cpp")) and os.path.basename(dirpath) == "csrc":
+                text = open(path).read()
+                found |= set(re.findall(r'\bgetenv\(\s*"([^"]+)"', text))
+                found |= set(re.findall(r'\bpn_env_u32\(\s*"([^"]+)"', text))
+            elif fn.endswith(".py"):
+                found |= set(re.findall(r'os\.environ\.get\(\s*"(PN_[^"]+)"', open(path).read()))
+    assert found == allow, f"read but not allowed: {sorted(found - allow)}; allowed but not read: {sorted(allow - found)}"
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    for name in sorted(allow):
+        assert f"`{name}`" in doc, f"{name} is read by the package but not listed in INTEGRATION.md"
