@@ -516,6 +516,22 @@ int pn_sim_drag_set(void* drag, int n_IP, int vid, int active, double scale, con
 int pn_sim_drag_unproject(const float* depth0, int W, int H, double x, double y, const double* intr4, const double* pose16, const float* ip_pos,
                           int n_IP, void* drag, double* work, void* stream);
 
+/* ------------------------------------------------------------------ meshing ---- */
+
+/* Marching cubes (nerf/utils.py:174-205 extract_geometry's mcubes.marching_cubes; csrc/pn_mesh.hip, INTEGRATION.md "Meshing").  `field` is a
+ * C-contiguous fp32 lattice [nx, ny, nz] (z fastest), every dimension >= 2, 3 nx ny nz < 2^31 and 5 (nx-1)(ny-1)(nz-1) < 2^31 (else PN_ERR_ARG;
+ * pn_mc_work_bytes returns 0).  A node is above when (double)f > threshold.  One vertex per crossed lattice edge, at lo + t on the edge's axis with
+ * t = (threshold - f0) / (f1 - f0) in fp64 from the lower endpoint; vertices in node order then axis, triangles in cell order then case-table
+ * order, pointing out of the above-threshold region.  No atomics: the output is a pure function of the field and the threshold.
+ * pn_mc_count enqueues the count and the scan and writes totals [2] = {V, T} (device int64); the caller reads them to size vertices [V,3] fp64
+ * (index space) and triangles [T,3] int32, then pn_mc_emit (V = 0 implies T = 0: nothing to emit).  `work`: pn_mc_work_bytes bytes, kept between
+ * the two calls with the same field and threshold. */
+uint64_t pn_mc_work_bytes(int nx, int ny, int nz);
+int pn_mc_count(const float* field, int nx, int ny, int nz, double threshold, void* work, int64_t* totals, void* stream);
+int pn_mc_emit(const float* field, int nx, int ny, int nz, double threshold, const void* work, double* vertices, int* triangles, void* stream);
+/* [host] The case table the kernels use: tri_count [256], tri_edges [256*15] (Bourke edge ids, -1 padded).  No GPU needed. */
+int pn_mc_case_table(uint8_t* tri_count, int8_t* tri_edges);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,6 +36,7 @@ UNITS = {
     "pn_grid_nd.hip": ["-ffp-contract=fast"],
     "pn_sim.hip": ["-ffp-contract=fast"],
     "pn_drag.hip": ["-ffp-contract=fast"],   # shares pn_sim_ip.h with pn_sim.hip: the same contraction, the same bits
+    "pn_mesh.hip": ["-ffp-contract=off"],  # marching cubes: the vertex formula rounds as written (tests/mc_reference.py restates it bit for bit)
     "pn_copier.hip": [],  # host code only: frame copies through the HSA runtime (links libhsa-runtime64)
 }
 

@@ -1,5 +1,6 @@
-"""``get_rays`` and ``get_pnts_in_grids`` with the reference's signatures (nerf/utils.py:54-138, 355-386),
-backed by HIP kernels.  The rest of the reference's nerf/utils.py (metrics, meshing, seeding) is off-path."""
+"""``get_rays``, ``get_pnts_in_grids`` and the meshing functions ``extract_fields``, ``extract_geometry`` and ``write_to_ply`` with the reference's
+signatures (nerf/utils.py:54-138, 355-386, 174-205, 341-351), backed by HIP kernels: the density lattice is evaluated and meshed on the device
+(pienerf_amd.mesh, marching cubes in csrc/pn_mesh.hip).  The rest of the reference's nerf/utils.py (metrics, seeding) is off-path."""
 import numpy as np
 import torch
 
@@ -40,3 +41,39 @@ def get_pnts_in_grids(n_vtx, n_grid, pnts, bbmin, bbmax, hgs, resolution):
     check(lib().pn_pnts_in_grids(n_vtx, n_grid, ptr(pnts), ptr(bbmin), float(hgs), ptr(resolution), ptr(pig_cnt), ptr(pig_bgn), ptr(pig_idx),
                                  ptr(err), stream_ptr()), "get_pnts_in_grids")
     return pig_cnt, pig_bgn, pig_idx
+
+
+def extract_fields(bound_min, bound_max, resolution, query_func, S=128):
+    """nerf/utils.py:174-189: query_func on the resolution^3 lattice over [bound_min, bound_max] -> numpy float32 [res, res, res].  The lattice is
+    built and queried on the device (pienerf_amd.mesh.lattice_field); only the result is copied back."""
+    from ..mesh import lattice_field
+    return lattice_field(bound_min, bound_max, resolution, query_func, S=S).cpu().numpy()
+
+
+def extract_geometry(bound_min, bound_max, resolution, threshold, query_func):
+    """nerf/utils.py:192-205: (vertices float64 [V,3] in world space, triangles int64 [T,3]) of the `threshold` level set of query_func.  Field and
+    marching cubes stay on the device (pienerf_amd.mesh); the triangulation is the project's own ("Meshing").  World mapping with
+    the reference's operations, order and types: index-space vertex / (resolution - 1), times the box's extent (bound_max - bound_min, taken in
+    float32), plus bound_min; every step in float64."""
+    from ..mesh import lattice_field, marching_cubes
+    idx, tri = marching_cubes(lattice_field(bound_min, bound_max, resolution, query_func), threshold)
+    origin = _host_bound(bound_min)
+    extent = _host_bound(bound_max) - origin              # float32 - float32, rounded once in float32
+    scaled = idx.cpu().numpy() / (resolution - 1.0)
+    world = scaled * extent.astype(np.float64) + origin.astype(np.float64)
+    return world, tri.cpu().numpy().astype(np.int64)
+
+
+def _host_bound(b):
+    """A corner of the box as a float32 numpy [3] (the reference passes a float32 tensor)."""
+    return (b.detach().cpu().numpy() if torch.is_tensor(b) else np.asarray(b)).astype(np.float32).reshape(3)
+
+
+def write_to_ply(points, save_path):
+    """nerf/utils.py:341-351: ASCII PLY of the points [N,3] as float64: a header of `ply`, `format ascii 1.0`, `element vertex N`, `property
+    float` x / y / z and `end_header`, then one line per point, its coordinates as Python's str of the float, separated by single spaces."""
+    rows = np.asarray(points, dtype=np.float64).reshape(-1, 3).tolist()
+    head = ["ply", "format ascii 1.0", f"element vertex {len(rows)}"] + [f"property float {c}" for c in "xyz"] + ["end_header"]
+    with open(save_path, "w") as f:
+        f.writelines(line + "\n" for line in head)
+        f.writelines("%s %s %s\n" % (x, y, z) for x, y, z in rows)

@@ -11,7 +11,7 @@ procedural stand-in built here, deterministically from a numpy seed:
                     (nerf/network.py:36-71) and a morton-ordered ``density_bitfield``
                     (nerf/renderer.py:94-111, raymarching.cu:1398-1399) rasterised from the solid;
   * camera        — ``OrbitCamera`` pose / intrinsics (nerf/gui.py:13-44);
-  * PLY IO        — reader/writer for the one-element vertex PLY (``plyfile`` is not installed).
+  * PLY IO        — reader/writer for the one-element vertex PLY (``plyfile`` is not installed) and a triangle-mesh writer.
 
 Pure numpy: no GPU, no torch, no oracle.
 """
@@ -89,6 +89,23 @@ def write_ply(path, cloud, binary=True, props=None):
         else:
             for r in rec:
                 f.write((" ".join(repr(float(v)) if isinstance(v, np.floating) else str(int(v)) for v in r) + "\n").encode())
+
+
+def write_mesh_ply(path, vertices, triangles):
+    """Triangle mesh PLY, binary little endian: vertex `float` x, y, z and face `list uchar int vertex_indices` (Trainer.save_mesh's file; the
+    reference writes it with trimesh, which is believed to use this layout: not checked, trimesh is not available to compare against).  read_ply
+    reads its vertex element."""
+    v = np.ascontiguousarray(np.asarray(vertices), dtype="<f4").reshape(-1, 3)
+    t = np.asarray(triangles).reshape(-1, 3)
+    face = np.zeros(len(t), dtype=[("n", "u1"), ("i", "<i4", (3,))])
+    face["n"] = 3
+    face["i"] = t
+    hdr = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}", "property float x", "property float y", "property float z",
+           f"element face {len(t)}", "property list uchar int vertex_indices", "end_header"]
+    with open(path, "wb") as f:
+        f.write(("\n".join(hdr) + "\n").encode())
+        f.write(v.tobytes())
+        f.write(face.tobytes())
 
 
 def read_ply(path):

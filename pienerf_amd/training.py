@@ -7,9 +7,11 @@ Reference: main_train.py:60-80 (Adam(get_params(lr), betas=(0.9, 0.99), eps=1e-1
 (there is no dataset on the box): ``RayImageSet`` samples ``num_rays`` random pixels of a random view per step like
 nerf/provider.py's training collate (one view per batch, rays drawn uniformly, :270-300).
 """
+import os
+
 import torch
 
-from .nerf.utils import get_rays
+from .nerf.utils import extract_geometry, get_rays, write_to_ply
 
 
 class RayImageSet:
@@ -143,3 +145,29 @@ class Trainer:
         gt = img[..., :3] * img[..., 3:] + (1 - img[..., 3:]) if img.shape[-1] == 4 else img
         mse = torch.mean((out["image"].view(dataset.H, dataset.W, 3) - gt) ** 2)
         return float(-10 * torch.log10(mse)), out
+
+    def _geometry(self, resolution, threshold):
+        from .mesh import density_query
+        m = self.model
+        return extract_geometry(m.aabb_infer[:3], m.aabb_infer[3:], resolution=resolution, threshold=threshold, query_func=density_query(m, self.fp16))
+
+    def save_mesh(self, save_path, resolution=256, threshold=10):
+        """trainer.py:331-354: the `threshold` level set of model.density(pts)['sigma'] (no_grad, autocast(enabled=fp16)) on the resolution^3 lattice
+        over aabb_infer, meshed on the device, written as a binary PLY (scene.write_mesh_ply).  `save_path` is required: this Trainer has no workspace
+        or epoch to name a default file after."""
+        from .scene import write_mesh_ply
+        d = os.path.dirname(save_path)
+        if d:
+            os.makedirs(d, exist_ok=True)
+        vertices, triangles = self._geometry(resolution, threshold)
+        write_mesh_ply(save_path, vertices, triangles)
+        return vertices, triangles
+
+    def save_point_cloud(self, save_path, resolution=256, threshold=10):
+        """trainer.py:356-378: the vertices of save_mesh's surface as an ASCII PLY (write_to_ply).  `save_path` is required (no workspace / epoch)."""
+        d = os.path.dirname(save_path)
+        if d:
+            os.makedirs(d, exist_ok=True)
+        cloud, _ = self._geometry(resolution, threshold)
+        write_to_ply(cloud, save_path)
+        return cloud
