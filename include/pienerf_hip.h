@@ -209,6 +209,37 @@ int pn_nerf_sigma(const pn_net* net, const float* xyzs, uint32_t M, float densit
 /* [host] fp32 -> fp16 bit patterns, round to nearest even: the rounding the host side of pn_net_create applies to the weights. */
 int pn_host_float_to_half(const float* in_host, uint16_t* out_host, uint32_t n);
 
+/* ------------------------------------------------------------------ background model -- */
+
+/* The background model of NeRFNetwork with bg_radius > 0 (nerf/network.py:73-95,148-164; nerf/renderer.py:283-288, 799-801, 896), one launch per frame
+ * (csrc/pn_background.hip): ray -> exit point on the sphere of `radius` as (theta, phi) in [-1, 1] (the arithmetic of pn_sph_from_ray, bit for bit)
+ * -> 2-D grid encoder (4 levels x 2 features, inputs (x + 1) / 2) -> cat([SH degree 4 of rays_d, grid features]) -> Linear 24 -> 64, ReLU -> Linear 64 -> 3
+ * -> sigmoid.  pn_bg_net_create packs W0 [64,24] and W1 [3,64] (row-major [out,in], host) and the level geometry; `embeddings` (device, [offsets[L], 2]
+ * fp32) is read in place, not copied.  L must be 4 and C 2; every level either fully dense or hashed into a power-of-two table (else PN_ERR_ARG).
+ * pn_bg_net_update refreshes the packed weights in place after the parameters changed: host packing into pinned staging + one asynchronous upload on
+ * `stream`, one stream synchronisation (the table's largest entry chooses the fp16 pieces' scale), no allocation.  Both are PN_ERR_ARG while `stream` is
+ * being captured. */
+typedef struct pn_bg_net pn_bg_net;
+int pn_bg_net_create(pn_bg_net** out, const float* embeddings, const int* offsets_host /*[L+1]*/, uint32_t L, uint32_t C, float per_level_scale_log2,
+                     uint32_t base_resolution, const float* W0_host, const float* W1_host, void* stream);
+int pn_bg_net_update(pn_bg_net* net, const float* embeddings, const float* W0_host, const float* W1_host, void* stream);
+void pn_bg_net_destroy(pn_bg_net* net);
+/* rays_o, rays_d [N,3].  Two modes: rgb_out [N,3] != NULL (weights_sum == image == NULL) receives the colour; or weights_sum [N] and image [N,3] != NULL
+ * (rgb_out == NULL): image = image + (1 - weights_sum) * rgb IN PLACE, the multiply and the add rounded separately (torch's two ops, bit for bit given the
+ * same rgb).  coords_out [N,2] (may be NULL): the (theta, phi) the kernel used, for tests.  fp32-accurate (fp16 hi + lo pieces on the matrix cores, 2e-6
+ * on the colour against sequential fp32 sums).  No host synchronisation, no allocation: legal inside a HIP-graph capture; a captured launch follows
+ * pn_bg_net_update.  N <= (2^31 - 1) / 3. */
+int pn_background_forward(const pn_bg_net* net, const float* rays_o, const float* rays_d, uint32_t N, float radius, float* rgb_out,
+                          const float* weights_sum, float* image, float* coords_out, void* stream);
+/* The same as the reference computes it under autocast (half table entries, kernel_grid<at::Half>'s half accumulation, half Linear layers with fp32
+ * accumulation, half sigmoid): the colours are half values held in fp32. */
+int pn_background_forward_half(const pn_bg_net* net, const float* rays_o, const float* rays_d, uint32_t N, float radius, float* rgb_out,
+                               const float* weights_sum, float* image, float* coords_out, void* stream);
+
+/* NeRFNetwork.background(x, d) (nerf/network.py:148-164) on coordinates the caller already has: coords [N,2] in [-1,1], dirs [N,3] -> rgb_out [N,3]; the
+ * same kernel with the coordinate read instead of derived.  half != 0: the autocast form. */
+int pn_background_coords(const pn_bg_net* net, const float* coords, const float* dirs, uint32_t N, float* rgb_out, int half, void* stream);
+
 /* ------------------------------------------------------------------ whole frame ---- */
 
 /* NeRFRenderer.rund_cuda (nerf/renderer.py:755-907) for one frame with no host synchronisation inside the loop:

@@ -43,6 +43,36 @@ static inline uint32_t pn_env_u32(const char* name, uint32_t dflt) {
     return x > 0 ? (uint32_t)x : dflt;
 }
 
+// fp32 -> fp16, round to nearest even (what `tensor.to(torch.half)` and v_cvt_f16_f32 do), returned as the 16 payload bits
+static inline uint16_t pn_f2h_bits(float f) {
+    uint32_t x;
+    memcpy(&x, &f, 4);
+    const uint32_t sign = (x >> 16) & 0x8000u;
+    x &= 0x7fffffffu;
+    if (x >= 0x7f800000u) return (uint16_t)(sign | 0x7c00u | ((x > 0x7f800000u) ? 0x200u : 0u));  // inf / nan
+    if (x >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);                                        // rounds to >= 65520 -> inf
+    if (x < 0x33000001u) return (uint16_t)sign;                                                     // <= 2^-25 -> 0 (ties to even)
+    int e = (int)(x >> 23) - 127;
+    uint32_t m = (x & 0x7fffffu) | 0x800000u;  // 24-bit significand
+    int shift = (e < -14) ? (13 + (-14 - e)) : 13;  // bits dropped (subnormal halves drop more)
+    uint32_t q = m >> shift, rem = m & ((1u << shift) - 1u), halfway = 1u << (shift - 1);
+    if (rem > halfway || (rem == halfway && (q & 1u))) q++;
+    if (e < -14) return (uint16_t)(sign | q);  // subnormal (q may carry into the smallest normal: the encoding is continuous)
+    return (uint16_t)(sign | (((uint32_t)(e + 15) << 10) + (q - 0x400u)));  // mantissa carry rolls into the exponent
+}
+static inline float pn_h2f(uint16_t h) {
+    const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, e = (h >> 10) & 31u, m = h & 0x3ffu;
+    uint32_t x;
+    if (e == 0) {
+        if (m == 0) x = sign;
+        else { float v = (float)m * 5.9604644775390625e-8f; memcpy(&x, &v, 4); x |= sign; }  // m * 2^-24
+    } else if (e == 31) x = sign | 0x7f800000u | (m << 13);
+    else x = sign | ((e + 112u) << 23) | (m << 13);
+    float f;
+    memcpy(&f, &x, 4);
+    return f;
+}
+
 // Per-level geometry of the multiresolution hash grid, derived on the host with the reference's formulas
 // (gridencoder/src/gridencoder.cu:132-134) so that host libm — not the GPU's approximate exp2 — fixes
 // `scale` and `resolution` bit-for-bit.
@@ -114,6 +144,9 @@ struct pn_net {
 #define PN_NET_X_W_BYTES (PN_NET_GROUPS * 2 * 64 * 16)
 #define PN_NET_X_BYTES (PN_NET_X_W_BYTES + 192 * 4)
 
+// largest |entry| of a table of n floats as the bit pattern of a non-negative float (NaN counts as infinite), atomicMax'ed into *out (device word the caller
+// has zeroed on `st`); pn_nerf_forward.hip.  Shared by the two packed contexts (pn_net, pn_bg_net): it chooses the fp16 hi/lo form's scales.
+int pn_table_absmax_launch(const float* emb, uint32_t n, unsigned* out, hipStream_t st);
 // internal launcher shared by pn_nerf_forward and the frame driver: evaluates the network on the `count` samples whose
 // slot ids are list[0..count) (list == NULL: slots 0..M-1); when ctl_count != NULL the count is read from device memory.
 // half != 0: the fp16 form (fp16 tables, fp16 MFMA, half-rounded activations); requires pn_net_enable_half to have been called.

@@ -253,36 +253,6 @@ static void pack_weights(const float* W0, const float* W1, const float* W2, cons
             for (int l = 0; l < 64; l++) wp[m * 64 + l] = W3[(t * 32 + (l & 31)) * 64 + krow(q, l >> 5)];
 }
 
-// fp32 -> fp16, round to nearest even (what `tensor.to(torch.half)` and v_cvt_f16_f32 do), returned as the 16 payload bits
-static uint16_t pn_f2h_bits(float f) {
-    uint32_t x;
-    memcpy(&x, &f, 4);
-    const uint32_t sign = (x >> 16) & 0x8000u;
-    x &= 0x7fffffffu;
-    if (x >= 0x7f800000u) return (uint16_t)(sign | 0x7c00u | ((x > 0x7f800000u) ? 0x200u : 0u));  // inf / nan
-    if (x >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);                                        // rounds to >= 65520 -> inf
-    if (x < 0x33000001u) return (uint16_t)sign;                                                     // <= 2^-25 -> 0 (ties to even)
-    int e = (int)(x >> 23) - 127;
-    uint32_t m = (x & 0x7fffffu) | 0x800000u;  // 24-bit significand
-    int shift = (e < -14) ? (13 + (-14 - e)) : 13;  // bits dropped (subnormal halves drop more)
-    uint32_t q = m >> shift, rem = m & ((1u << shift) - 1u), halfway = 1u << (shift - 1);
-    if (rem > halfway || (rem == halfway && (q & 1u))) q++;
-    if (e < -14) return (uint16_t)(sign | q);  // subnormal (q may carry into the smallest normal: the encoding is continuous)
-    return (uint16_t)(sign | (((uint32_t)(e + 15) << 10) + (q - 0x400u)));  // mantissa carry rolls into the exponent
-}
-static float pn_h2f(uint16_t h) {
-    const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, e = (h >> 10) & 31u, m = h & 0x3ffu;
-    uint32_t x;
-    if (e == 0) {
-        if (m == 0) x = sign;
-        else { float v = (float)m * 5.9604644775390625e-8f; memcpy(&x, &v, 4); x |= sign; }  // m * 2^-24
-    } else if (e == 31) x = sign | 0x7f800000u | (m << 13);
-    else x = sign | ((e + 112u) << 23) | (m << 13);
-    float f;
-    memcpy(&f, &x, 4);
-    return f;
-}
-
 // Both LDS weight images from the five row-major [out,in] matrices.
 //   simg (PN_NET_SPLIT_BYTES): operand group (layer, out tile t, K chunk kc) takes the 8 consecutive activation registers m0 + 8 kc + e
 //     (e = 0..7) of pack_weights' stream as the 8 K-elements of its lane, each weight cut into three bf16 pieces w = hi + mid + lo
@@ -372,6 +342,12 @@ __global__ void __launch_bounds__(256) k_table_absmax(const float* __restrict__ 
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
     if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
+}
+
+int pn_table_absmax_launch(const float* emb, uint32_t n, unsigned* out, hipStream_t st) {
+    k_table_absmax<<<512, 256, 0, st>>>(emb, n, out);
+    PN_LAUNCH_CHECK();
+    return PN_OK;
 }
 
 // Whether the fp16 hi/lo form runs for these weights and tables (pn_common.h: pn_net::x_ok), and the power-of-two scale every layer's inputs are carried

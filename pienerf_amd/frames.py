@@ -64,6 +64,25 @@ def broadcast_tensors(tensors, src=0, group=None):
         dist.broadcast(t, src=src, group=group)
 
 
+def checkpoint_tensors(model):
+    """The tensors of a NeRFNetwork that the one-off checkpoint broadcast carries, in a fixed order: hash table, density bitfield, the five layers'
+    weights and — when the model has a background network (bg_radius > 0) — its 2-D table and two weights, so that ranks other than `src` do not
+    render a randomly initialised sky."""
+    ts = [model.encoder.embeddings.data, model.density_bitfield] + [l.weight.data for l in list(model.sigma_net) + list(model.color_net)]
+    if getattr(model, "bg_net", None) is not None:
+        ts += [model.encoder_bg.embeddings.data] + [l.weight.data for l in model.bg_net]
+    return ts
+
+
+def broadcast_checkpoint(model, src=0, group=None):
+    """broadcast_tensors(checkpoint_tensors(model)), then both packed weight images of the fused kernels are marked stale: a receive into `.data` does not
+    move the parameters' version counters, which is what the images otherwise follow."""
+    broadcast_tensors(checkpoint_tensors(model), src=src, group=group)
+    for stamp in ("_net_sig", "_bg_sig"):
+        if hasattr(model, stamp):
+            setattr(model, stamp, None)
+
+
 def tile_partition(W, H, world, tile=8):
     """Ray-tile-parallel split of ONE frame ("alternative for interactive latency"): the image is cut into tile x tile pixel
     blocks, block b (row-major) goes to rank b % world, so that every rank gets an interleaved 1/world of the object and of the background.

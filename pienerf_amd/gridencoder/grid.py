@@ -47,7 +47,8 @@ class _grid_encode(torch.autograd.Function):
         if offsets_host is None:
             offsets_host = offsets.detach().to("cpu", torch.int32).contiguous()
         log2_scale = float(np.float32(np.log2(per_level_scale)))  # the reference passes S = log2(per_level_scale) as a float (grid.py:37)
-        if (torch.is_autocast_enabled() and C % 2 == 0) or embeddings.dtype == torch.float16:  # grid.py:41-44
+        half = (torch.is_autocast_enabled() and C % 2 == 0) or embeddings.dtype == torch.float16  # grid.py:41-44
+        if half and D == 3:
             if calc_grad_inputs:
                 raise RuntimeError("grid_encode: input gradients are not built on the half-precision path; disable autocast for them")
             table = embeddings.detach().to(torch.float16).contiguous()
@@ -68,6 +69,9 @@ class _grid_encode(torch.autograd.Function):
             else:
                 ctx.mark_non_differentiable(feats)
             return feats
+        # fp32 kernels; also the half case of D = 2, 4, 5 (the background model's 2-D grid under --fp16): the half kernels exist for D = 3 only, so the
+        # table is read in fp32 and the features are rounded to half once at the end (within a half ulp or two of kernel_grid<at::Half>'s running half sum);
+        # the backward is then the fp32 scatter-add, its result cast to the parameter's type
         table = embeddings.to(torch.float32).contiguous()
         require_gpu(x, table)
         feats = torch.empty(B, n_levels * C, device=x.device, dtype=torch.float32)
@@ -80,7 +84,8 @@ class _grid_encode(torch.autograd.Function):
         ctx.dims = [B, D, C, n_levels, log2_scale, int(base_resolution), int(gridtype), int(interpolation)]
         ctx.align_corners = bool(align_corners)
         ctx.offsets_host = offsets_host
-        return feats
+        ctx.table_dtype = embeddings.dtype
+        return feats.to(torch.float16) if half else feats
 
     @staticmethod
     def backward(ctx, grad):
@@ -100,7 +105,7 @@ class _grid_encode(torch.autograd.Function):
         rc = lib().pn_grid_encode_backward(ptr(grad), ptr(x), ptr(table), ctx.offsets_host.data_ptr(), ptr(grad_embeddings), B, D, C, L, S, H, ptr(dy_dx),
                                            ptr(grad_inputs), gridtype, int(ctx.align_corners), interpolation, stream_ptr())
         check(rc, "grid_encode_backward")
-        return grad_inputs, grad_embeddings, None, None, None, None, None, None, None, None, None
+        return grad_inputs, grad_embeddings.to(ctx.table_dtype), None, None, None, None, None, None, None, None, None
 
 
 def grid_encode(inputs, embeddings, offsets, per_level_scale, base_resolution, calc_grad_inputs=False, gridtype=0, align_corners=False,

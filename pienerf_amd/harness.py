@@ -49,7 +49,7 @@ class SimRenderHarness:
         o = self.opt
         self.device = torch.device(device)
         self.cloud = cloud if cloud is not None else scene.make_chair_points(hgs=o["hash_grid_size"], bound=o["bound"])
-        self.ckpt = ckpt if ckpt is not None else scene.make_checkpoint(bound=o["bound"])
+        self.ckpt = ckpt if ckpt is not None else scene.make_checkpoint(bound=o["bound"], bg_radius=o["bg_radius"])
         # main_gui.py:26-34
         self.model = NeRFNetwork(encoding="hashgrid", bound=o["bound"], cuda_ray=True, density_scale=1, min_near=o["min_near"],
                                  density_thresh=o["density_thresh"], bg_radius=o["bg_radius"]).to(self.device)

@@ -96,6 +96,8 @@ def load_checkpoint(model, path, model_only=True, optimizer=None, lr_scheduler=N
             ema.load_state_dict(ck["ema"])
     if hasattr(model, "_net_sig"):
         model._net_sig = None  # the packed weight image of the fused kernel is rebuilt on next use
+    if hasattr(model, "_bg_sig"):
+        model._bg_sig = None   # likewise the background model's
     model.eval()
     return info
 

@@ -23,7 +23,7 @@ from .harness import SimRenderHarness
 def build_harness(args):
     opt = scene.default_opt(W=args.W, H=args.H, radius=args.radius, fovy=args.fovy, sim_dx=args.sim_dx, sim_iters=args.sim_iters,
                             max_iter_num=args.max_iter_num, num_seek_IP=args.num_seek_IP, bound=args.bound, dt_gamma=args.dt_gamma,
-                            max_steps=args.max_steps, T_thresh=args.T_thresh)
+                            max_steps=args.max_steps, T_thresh=args.T_thresh, bg_radius=args.bg_radius)
     cloud = scene.cloud_from_ply(args.ply) if args.ply else None
     h = SimRenderHarness(opt, cloud=cloud, ckpt=None, device=args.device)
     if args.ckpt:
@@ -90,6 +90,7 @@ def parser():
     ap.add_argument("--elevation", type=float, default=0.0)
     ap.add_argument("--fovy", type=float, default=50.0)
     ap.add_argument("--bound", type=float, default=1.0)
+    ap.add_argument("--bg_radius", type=float, default=-1, help="> 0: the checkpoint's background model colours each ray where it leaves the sphere of this radius")
     ap.add_argument("--dt_gamma", type=float, default=0.0)
     ap.add_argument("--max_steps", type=int, default=1024)
     ap.add_argument("--T_thresh", type=float, default=1e-2)

@@ -91,9 +91,10 @@ def main(argv=None):
     ap.add_argument("--threshold", type=float, default=10.0)
     ap.add_argument("--fp16", action="store_true", help="query the density under autocast (Trainer(fp16=True))")
     ap.add_argument("--bound", type=float, default=1.0)
+    ap.add_argument("--bg_radius", type=float, default=-1, help="> 0: the checkpoint holds a background model (its tensors are loaded; meshing does not use them)")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args(argv)
-    model = NeRFNetwork(encoding="hashgrid", bound=args.bound, cuda_ray=True, density_scale=1, min_near=0.2, density_thresh=10, bg_radius=-1)
+    model = NeRFNetwork(encoding="hashgrid", bound=args.bound, cuda_ray=True, density_scale=1, min_near=0.2, density_thresh=10, bg_radius=args.bg_radius)
     model = model.to(args.device)
     if args.ckpt:
         path = args.ckpt if os.path.isfile(args.ckpt) else io.latest_checkpoint(args.ckpt)

@@ -21,8 +21,6 @@ class NeRFNetwork(NeRFRenderer):
     def __init__(self, encoding="hashgrid", encoding_dir="sphere_harmonics", encoding_bg="hashgrid", num_layers=2, hidden_dim=64, geo_feat_dim=15,
                  num_layers_color=3, hidden_dim_color=64, num_layers_bg=2, hidden_dim_bg=64, bound=1, **kwargs):
         super().__init__(bound, **kwargs)
-        if self.bg_radius > 0:
-            raise NotImplementedError("background model (bg_radius > 0) is not on the simulate-and-render path (main_gui.py uses -1)")
         self.num_layers, self.hidden_dim, self.geo_feat_dim = num_layers, hidden_dim, geo_feat_dim
         self.encoder, self.in_dim = get_encoder(encoding, desired_resolution=2048 * bound)
         dims = [self.in_dim] + [hidden_dim] * (num_layers - 1) + [1 + geo_feat_dim]  # 1 sigma + 15 geo features
@@ -31,7 +29,16 @@ class NeRFNetwork(NeRFRenderer):
         self.encoder_dir, self.in_dim_dir = get_encoder(encoding_dir)
         cdims = [self.in_dim_dir + geo_feat_dim] + [hidden_dim_color] * (num_layers_color - 1) + [3]
         self.color_net = nn.ModuleList([nn.Linear(cdims[i], cdims[i + 1], bias=False) for i in range(num_layers_color)])
-        self.bg_net = None
+        if self.bg_radius > 0:  # network.py:73-95: a much smaller 2-D grid over (theta, phi) + the view direction's SH -> 2 bias-free layers
+            self.num_layers_bg, self.hidden_dim_bg = num_layers_bg, hidden_dim_bg
+            self.encoder_bg, self.in_dim_bg = get_encoder(encoding_bg, input_dim=2, num_levels=4, log2_hashmap_size=19, desired_resolution=2048)
+            bdims = [self.in_dim_bg + self.in_dim_dir] + [hidden_dim_bg] * (num_layers_bg - 1) + [3]
+            self.bg_net = nn.ModuleList([nn.Linear(bdims[i], bdims[i + 1], bias=False) for i in range(num_layers_bg)])
+        else:
+            self.bg_net = None
+        self._bg = None
+        self._bg_sig = None
+        self._bg_dev = None
         self._net = None
         self._net_sig = None
         self._net_dev = None
@@ -78,6 +85,39 @@ class NeRFNetwork(NeRFRenderer):
             check(lib().pn_net_enable_half(self._net, stream_ptr()), "net_enable_half")
             self._net_half = True
         return self._net
+
+    def _bg_handle(self):
+        """The background model's packed device context (pn_bg_net), handled like ``_net_handle``: created on first use, refreshed in place when a
+        parameter changed, refused while pipelined frames are in flight and during stream capture.  One image serves the fp32 and the fp16 form."""
+        ts = [self.encoder_bg.embeddings] + [l.weight for l in self.bg_net]
+        sig = tuple((t.data_ptr(), t._version, str(t.device)) for t in ts)
+        if self._bg is not None and sig == self._bg_sig:
+            return self._bg
+        if self._bg is not None and getattr(self, "_in_flight", None) is not None and self._in_flight() > 0:
+            raise RuntimeError("the background model's parameters changed while pipelined frames are in flight: drain_pipeline() before updating weights")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("the background model's parameters changed and its packed weights cannot be refreshed while the stream is being captured "
+                               "into a HIP graph (the packing reads them on the host); evaluate the background once before capture")
+        enc = self.encoder_bg
+        if (self.num_layers_bg, self.hidden_dim_bg, enc.input_dim, enc.num_levels, enc.level_dim, self.in_dim_dir) != (2, 64, 2, 4, 2, 16):
+            raise RuntimeError("fused background kernel implements the reference architecture only (2-D grid 4x2 + SH16 -> 64 -> 3)")
+        emb = enc.embeddings
+        require_gpu(emb)
+        assert emb.dtype == torch.float32 and emb.is_contiguous()
+        Ws = [np.ascontiguousarray(l.weight.detach().cpu().numpy(), dtype=np.float32) for l in self.bg_net]
+        if self._bg is None or self._bg_dev != str(emb.device):
+            if self._bg is not None:
+                lib().pn_bg_net_destroy(self._bg)
+                self._bg = None
+            h = C.c_void_p()
+            check(lib().pn_bg_net_create(C.byref(h), ptr(emb), enc._offsets_host.data_ptr(), enc.num_levels, enc.level_dim,
+                                         float(np.float32(np.log2(enc.per_level_scale))), int(enc.base_resolution), Ws[0].ctypes.data, Ws[1].ctypes.data,
+                                         stream_ptr()), "bg_net_create")
+            self._bg, self._bg_dev = h, str(emb.device)
+        else:
+            check(lib().pn_bg_net_update(self._bg, ptr(emb), Ws[0].ctypes.data, Ws[1].ctypes.data, stream_ptr()), "bg_net_update")
+        self._bg_sig = sig
+        return self._bg
 
     @staticmethod
     def _autocast_half():
@@ -152,10 +192,65 @@ class NeRFNetwork(NeRFRenderer):
                 h = F.relu(h, inplace=True)
         return sigma, torch.sigmoid(h)
 
+    # ---- background model (network.py:148-164), bg_radius > 0
+    def background(self, x, d):
+        """x [N,2] in [-1,1] (sph_from_ray), d [N,3] -> rgb [N,3] (network.py:148-164).  With autograd recording in train() mode: the differentiable op
+        sequence ``background_ops``; otherwise one fused launch (pn_background_coords), under fp16 autocast its half form, returning a half tensor like
+        the reference's sigmoid of a half input.  The renders do not come here: they hand the rays to the same kernel, which derives the coordinate
+        itself and blends in place (``blend_background``)."""
+        if self.bg_net is None:
+            raise RuntimeError("background(): the model was built without a background network (bg_radius <= 0)")
+        if self._wants_grad(x, d):
+            return self.background_ops(x, d)
+        x = x.to(torch.float32).contiguous().view(-1, 2)
+        d = d.to(torch.float32).contiguous().view(-1, 3)
+        require_gpu(x, d)
+        assert x.shape[0] == d.shape[0]
+        half = self._autocast_half()
+        rgb = torch.empty(x.shape[0], 3, dtype=torch.float32, device=x.device)
+        check(lib().pn_background_coords(self._bg_handle(), ptr(x), ptr(d), x.shape[0], ptr(rgb), int(half), stream_ptr()), "background_coords")
+        return rgb.to(torch.float16) if half else rgb
+
+    def _background_launch(self, rays_o, rays_d, rgb, weights_sum, image, coords):
+        fn = lib().pn_background_forward_half if self._autocast_half() else lib().pn_background_forward
+        check(fn(self._bg_handle(), ptr(rays_o), ptr(rays_d), rays_o.shape[0], float(self.bg_radius), ptr(rgb), ptr(weights_sum), ptr(image), ptr(coords),
+                 stream_ptr()), "background_forward")
+
+    def background_rays(self, rays_o, rays_d, return_coords=False):
+        """The background colour [N,3] of rays [N,3] (fp32, contiguous, on the GPU): sph_from_ray + background() in one launch.  return_coords: also the
+        (theta, phi) [N,2] the kernel used (bit for bit raymarching.sph_from_ray's)."""
+        require_gpu(rays_o, rays_d)
+        rgb = torch.empty(rays_o.shape[0], 3, dtype=torch.float32, device=rays_o.device)
+        coords = torch.empty(rays_o.shape[0], 2, dtype=torch.float32, device=rays_o.device) if return_coords else None
+        self._background_launch(rays_o, rays_d, rgb, None, None, coords)
+        return (rgb, coords) if return_coords else rgb
+
+    def blend_background(self, rays_o, rays_d, weights_sum, image):
+        """image += (1 - weights_sum) * background, IN PLACE in `image` [N,3] (renderer.py:288, :896 with the model's colour): the fused renders' last
+        launch, on the current stream; no allocation, no host synchronisation once the packed weights exist."""
+        require_gpu(rays_o, rays_d, weights_sum, image)
+        assert image.shape == (rays_o.shape[0], 3) and weights_sum.shape == (rays_o.shape[0],)
+        assert all(t.dtype == torch.float32 for t in (image, weights_sum))
+        self._background_launch(rays_o, rays_d, None, weights_sum, image, None)
+
+    def background_ops(self, x, d):
+        """The reference's op sequence: GridEncoder (D = 2, default bound 1) | SHEncoder, cat (SH first) -> Linear/ReLU -> Linear -> sigmoid."""
+        h = self.encoder_bg(x)
+        h = torch.cat([self.encoder_dir(d), h], dim=-1)
+        for i, layer in enumerate(self.bg_net):
+            h = layer(h)
+            if i != self.num_layers_bg - 1:
+                h = F.relu(h, inplace=True)
+        return torch.sigmoid(h)
+
     def get_params(self, lr):
         """network.py:196-207: optimizer parameter groups."""
-        return [{"params": self.encoder.parameters(), "lr": lr}, {"params": self.sigma_net.parameters(), "lr": lr},
-                {"params": self.encoder_dir.parameters(), "lr": lr}, {"params": self.color_net.parameters(), "lr": lr}]
+        params = [{"params": self.encoder.parameters(), "lr": lr}, {"params": self.sigma_net.parameters(), "lr": lr},
+                  {"params": self.encoder_dir.parameters(), "lr": lr}, {"params": self.color_net.parameters(), "lr": lr}]
+        if self.bg_radius > 0:
+            params.append({"params": self.encoder_bg.parameters(), "lr": lr})
+            params.append({"params": self.bg_net.parameters(), "lr": lr})
+        return params
 
     def load_checkpoint_dict(self, ck):
         """Loads the synthetic checkpoint dict of pienerf_amd.scene.make_checkpoint (same tensors as the reference's
@@ -167,5 +262,10 @@ class NeRFNetwork(NeRFRenderer):
             for layer, key in zip(list(self.sigma_net) + list(self.color_net), ("W0", "W1", "W2", "W3", "W4")):
                 layer.weight.copy_(torch.from_numpy(ck[key]).to(dev))
             self.density_bitfield.copy_(torch.from_numpy(ck["density_bitfield"]).to(dev))
+            if self.bg_net is not None and "bg_embeddings" in ck:   # make_checkpoint(..., bg_radius=R): encoder_bg.embeddings, bg_net.{0,1}.weight
+                assert tuple(self.encoder_bg.offsets.cpu().numpy()) == tuple(np.asarray(ck["bg_offsets"])), "background grid geometry mismatch"
+                self.encoder_bg.embeddings.copy_(torch.from_numpy(ck["bg_embeddings"]).to(dev))
+                for layer, key in zip(self.bg_net, ("bg_W0", "bg_W1")):
+                    layer.weight.copy_(torch.from_numpy(ck[key]).to(dev))
         self._net_sig = None
         return self.eval()  # a loaded checkpoint is used for inference; training code calls .train() itself

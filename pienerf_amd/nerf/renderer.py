@@ -53,6 +53,12 @@ class NeRFRenderer(nn.Module):
     def _net_handle(self, half=False):
         raise NotImplementedError()
 
+    def background(self, x, d):
+        raise NotImplementedError()
+
+    def blend_background(self, rays_o, rays_d, weights_sum, image):
+        raise NotImplementedError()
+
     @staticmethod
     def _autocast_half():
         return False
@@ -132,7 +138,7 @@ class NeRFRenderer(nn.Module):
         require_gpu(rays_o, rays_d)
         N, device = rays_o.shape[0], rays_o.device
         if self.bg_radius > 0:
-            raise RuntimeError("background model (bg_radius > 0) is not on the simulate-and-render path")
+            bg_color = 0   # the model's colour replaces whatever was passed (renderer.py:799-803): composite over 0, blend below
         if bg_color is None:
             bg_color = 1
         # a tensor background ([3] or [N,3], e.g. the GUI's bg_color tensor, gui.py:590): the driver composites over 0 and the blend
@@ -166,7 +172,9 @@ class NeRFRenderer(nn.Module):
                   "render_deformed")
             if stats is not None:
                 self._set_stats(stats)
-        if bg_tensor is not None:
+        if self.bg_radius > 0:
+            self.blend_background(rays_o, rays_d, weights_sum, image)   # in place: `image` may be the caller's out_buffers
+        elif bg_tensor is not None:
             image = image + (1 - weights_sum).unsqueeze(-1) * bg_tensor
         return {"depth": depth.view(*prefix), "image": image.view(*prefix, 3), "depth_0": depth_0.view(*prefix), "weights_sum": weights_sum}
 
@@ -174,10 +182,13 @@ class NeRFRenderer(nn.Module):
         """Finishes the frame last rendered on workspace `slot` with a fixed trip count that turned out too small (render_status reports
         rays alive at exit): more trips of the same loop — n_trips of them, or (0) until no ray is alive — and the epilogue again, into the
         SAME output tensors `out` (the dict the render returned).  The reference's loop has no trip limit but max_steps (renderer.py:836-891);
-        this is how the captured, fixed-length forms keep that semantics.  Blocking when n_trips == 0."""
+        this is how the captured, fixed-length forms keep that semantics.  Blocking when n_trips == 0.  With a background model the epilogue
+        composites over 0 again and the model's colour is blended in again, once."""
         rays_o = rays_o.to(torch.float32).contiguous().view(-1, 3)
         rays_d = rays_d.to(torch.float32).contiguous().view(-1, 3)
         N = rays_o.shape[0]
+        if self.bg_radius > 0:
+            bg_color = 0
         if static:
             o = RenderOpts()
             o.max_iter_num, o.hash_grid_size, o.num_seek_IP, o.IP_dx, o.cut = 1, 1.0, 1, 0.0, 0
@@ -193,6 +204,8 @@ class NeRFRenderer(nn.Module):
         check(lib().pn_render_continue(self._frames[slot][0], self._net_handle(half=bool(o.fp16)), C.byref(o), ptr(rays_o), ptr(rays_d), N,
                                        ptr(self.density_bitfield), ptr(image), ptr(depth), ptr(depth_0), ptr(ws), stats, int(n_trips), int(bool(static)),
                                        stream_ptr()), "render_continue")
+        if self.bg_radius > 0:
+            self.blend_background(rays_o, rays_d, ws, image)
         if stats is not None:
             self._set_stats(stats)
         return out
@@ -265,7 +278,7 @@ class NeRFRenderer(nn.Module):
                   stable compaction driven by a device-side trip record, with one 16-byte read-back per batch of 8 trips (the reference
                   synchronises the host on every trip, :351-380).  Per-ray background colours and ``perturb`` take the op-by-op loop
                   ``run_cuda_ops`` (same kernels, host-driven)."""
-        if not self.training and not perturb and not torch.is_tensor(bg_color):
+        if not self.training and not perturb and (self.bg_radius > 0 or not torch.is_tensor(bg_color)):
             return self._run_static_fused(rays_o, rays_d, dt_gamma, 1 if bg_color is None else bg_color, max_steps, T_thresh, **kwargs)
         return self.run_cuda_ops(rays_o, rays_d, dt_gamma, bg_color, perturb, force_all_rays, max_steps, T_thresh, **kwargs)
 
@@ -275,7 +288,7 @@ class NeRFRenderer(nn.Module):
         rays_d = rays_d.to(torch.float32).contiguous().view(-1, 3)
         require_gpu(rays_o, rays_d)
         if self.bg_radius > 0:
-            raise RuntimeError("background model (bg_radius > 0) is not built")
+            bg_color = 0   # renderer.py:283-288: the model's colour, blended in below
         N, device = rays_o.shape[0], rays_o.device
         o = RenderOpts()
         o.max_iter_num, o.hash_grid_size, o.num_seek_IP, o.IP_dx, o.cut = 1, 1.0, 1, 0.0, 0
@@ -290,6 +303,8 @@ class NeRFRenderer(nn.Module):
         stats = (C.c_int64 * 5)() if not async_trips else None
         check(lib().pn_render_static(frame, self._net_handle(half=bool(o.fp16)), C.byref(o), ptr(rays_o), ptr(rays_d), N, aabb, ptr(self.density_bitfield),
                                      ptr(image), ptr(depth), ptr(depth_0), ptr(ws), stats, async_trips, stream_ptr()), "render_static")
+        if self.bg_radius > 0:
+            self.blend_background(rays_o, rays_d, ws, image)
         if stats is not None:
             self._set_stats(stats)
         return {"depth": depth.view(*prefix), "image": image.view(*prefix, 3), "weights_sum": ws}
@@ -308,8 +323,8 @@ class NeRFRenderer(nn.Module):
         shape = rays_o.shape[:-1]
         o3, d3 = rays_o.contiguous().view(-1, 3), rays_d.contiguous().view(-1, 3)
         nears, fars = raymarching.near_far_from_aabb(o3, d3, self.aabb_train if self.training else self.aabb_infer, self.min_near)
-        if self.bg_radius > 0:
-            raise RuntimeError("background model (bg_radius > 0) is not built")
+        if self.bg_radius > 0:  # renderer.py:283-286: the model's colour; in train() mode through the differentiable ops
+            bg_color = self.background(raymarching.sph_from_ray(o3, d3, self.bg_radius), d3)
         bg = 1 if bg_color is None else bg_color
 
         def shade(xyzs, dirs):
@@ -430,7 +445,9 @@ class NeRFRenderer(nn.Module):
         resolution = torch.ceil((bbmax - bbmin) / hgs).to(torch.int32)
         aabb = torch.cat((bbmin, bbmax), dim=0)
         nears, fars = raymarching.near_far_from_aabb(rays_o, rays_d, aabb, self.min_near)
-        if bg_color is None:
+        if self.bg_radius > 0:  # renderer.py:799-801
+            bg_color = self.background(raymarching.sph_from_ray(rays_o, rays_d, self.bg_radius), rays_d)
+        elif bg_color is None:
             bg_color = 1
         weights_sum = torch.zeros(N, dtype=dtype, device=device)
         depth = torch.zeros(N, dtype=dtype, device=device)

@@ -195,7 +195,7 @@ def make_density_bitfield(bound=1.0, grid_size=128, solid=chair_solid):
     return bits, cascade
 
 
-def make_checkpoint(bound=1.0, seed=0, sigma_target=60.0, grid_size=128, solid=chair_solid, shaped=False, sigma_outside=0.02):
+def make_checkpoint(bound=1.0, seed=0, sigma_target=60.0, grid_size=128, solid=chair_solid, shaped=False, sigma_outside=0.02, bg_radius=-1):
     """Random-init network of the reference architecture with an analytically calibrated density:
 
     feature 0 (level 0, channel 0) is the constant 0.5 (level 0 is dense, so trilinear interpolation
@@ -205,6 +205,10 @@ def make_checkpoint(bound=1.0, seed=0, sigma_target=60.0, grid_size=128, solid=c
     shaped=True (point sampling, pienerf_amd/sampling.py): the density FIELD itself has the solid's shape, not only the bitfield —
     channel 0 of the finest dense level holds the solid's vertex occupancy, hidden unit 1 = its trilinear interpolation, and
     sigma = sigma_outside * (sigma_target / sigma_outside)^occupancy * exp(small random term).
+
+    bg_radius > 0: additionally the background model's tensors (nerf/network.py:73-95) — ``bg_embeddings`` ~ U(-0.5, 0.5) over the 2-D grid's
+    ``bg_offsets``, ``bg_W0`` [64, 24] and ``bg_W1`` [3, 64] ~ N(0, 2 / fan_in) — from a generator of their own, so that every other tensor keeps
+    the values it has without a background.
     """
     rng = np.random.default_rng(seed)
     offsets, pls = hashgrid_offsets(bound)
@@ -234,8 +238,16 @@ def make_checkpoint(bound=1.0, seed=0, sigma_target=60.0, grid_size=128, solid=c
         W1[0, 0] = math.log(sigma_outside)
         W1[0, 1] = math.log(sigma_target / sigma_outside)
     bits, cascade = make_density_bitfield(bound, grid_size, solid)
-    return dict(embeddings=emb, offsets=offsets, per_level_scale=pls, base_resolution=16, W0=W0, W1=W1, W2=W2, W3=W3, W4=W4,
-                density_bitfield=bits, cascade=cascade, grid_size=grid_size, bound=float(bound), min_near=0.2, density_scale=1.0)
+    ck = dict(embeddings=emb, offsets=offsets, per_level_scale=pls, base_resolution=16, W0=W0, W1=W1, W2=W2, W3=W3, W4=W4,
+              density_bitfield=bits, cascade=cascade, grid_size=grid_size, bound=float(bound), min_near=0.2, density_scale=1.0)
+    if bg_radius > 0:
+        brng = np.random.default_rng([int(seed), 0x6267])
+        bg_offsets, bg_pls = hashgrid_offsets(1.0, num_levels=4, input_dim=2)         # get_encoder(input_dim=2, num_levels=4, desired_resolution=2048)
+        ck.update(bg_radius=float(bg_radius), bg_offsets=bg_offsets, bg_per_level_scale=bg_pls,
+                  bg_embeddings=brng.uniform(-0.5, 0.5, size=(int(bg_offsets[-1]), 2)).astype(np.float32),
+                  bg_W0=(brng.standard_normal((64, 24)) * math.sqrt(2.0 / 24)).astype(np.float32),
+                  bg_W1=(brng.standard_normal((3, 64)) * math.sqrt(2.0 / 64)).astype(np.float32))
+    return ck
 
 
 # ------------------------------------------------------------------ camera

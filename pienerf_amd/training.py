@@ -98,10 +98,12 @@ class Trainer:
         """trainer.py:158-207 (the image-supervised branch)."""
         images = data["images"]
         C = images.shape[-1]
-        if C == 4:  # random per-pixel background under the alpha matte (trainer.py:193-196)
+        if C == 4 and not self.model.bg_radius > 0:  # random per-pixel background under the alpha matte (trainer.py:186-196); not with a background model
             bg_color = torch.rand_like(images[..., :3])
             gt_rgb = images[..., :3] * images[..., 3:] + bg_color * (1 - images[..., 3:])
             bg = bg_color.view(-1, 3)
+        elif C == 4:  # background model: the matte is composited over 1, the render's background is the model's whatever is passed (renderer.py:283-288)
+            bg, gt_rgb = 1, images[..., :3] * images[..., 3:] + (1 - images[..., 3:])
         else:
             bg, gt_rgb = 1, images
         outputs = self.model.render(data["rays_o"], data["rays_d"], staged=False, bg_color=bg, perturb=True, force_all_rays=False, **self._render_opts())
