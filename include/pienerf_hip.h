@@ -240,6 +240,28 @@ int pn_background_forward_half(const pn_bg_net* net, const float* rays_o, const 
  * same kernel with the coordinate read instead of derived.  half != 0: the autocast form. */
 int pn_background_coords(const pn_bg_net* net, const float* coords, const float* dirs, uint32_t N, float* rgb_out, int half, void* stream);
 
+/* NeRFNetwork.color(x, d, mask, geo_feat) (nerf/network.py:165-194; csrc/pn_hier.hip): rgbs [M,3] = sigmoid(colour net([SH16(dirs) | geo_feat])) on
+ * the rows whose mask byte is non-zero (mask == NULL: every row) and exact zeros elsewhere.  dirs [M,3], geo_feat [M,15] fp32 as pn_nerf_density wrote
+ * them, mask [M] bytes.  The matrix work is proportional to the number of masked rows (they are compacted into 32-row tiles per wave).  No host
+ * synchronisation, no allocation.  M <= (2^31 - 1) / 15.  _half: the autocast form (geo_feat holds half values, rgbs the half-rounded sigmoid outputs;
+ * needs pn_net_enable_half). */
+int pn_nerf_color(const pn_net* net, const float* dirs, const float* geo_feat, const uint8_t* mask, uint32_t M, float* rgbs, void* stream);
+int pn_nerf_color_half(const pn_net* net, const float* dirs, const float* geo_feat, const uint8_t* mask, uint32_t M, float* rgbs, void* stream);
+
+/* NeRFRenderer.run (nerf/renderer.py:137-265), the hierarchical-sampling render of a model without a density grid, eval() mode (det = True, no perturb),
+ * in one launch: per ray num_steps stratified samples between near and far of `aabb` ([host] six floats), their densities, upsample_steps samples drawn from
+ * the resulting weights (sample_pdf), their densities, the merge, the colour of the samples whose weight exceeds 1e-4, and the sums
+ *   weights_sum [N] = sum w,  depth [N] = sum w clamp((z - near) / (far - near), 0, 1)  (NaN for a ray that misses the box),
+ *   image [N,3] = sum w rgb + (1 - weights_sum) * background,  background = bg_rays [N,3] when not NULL, else bg_scalar (0: composite over nothing).
+ * One wave per ray, the sample set in LDS (csrc/pn_hier.hip): num_steps + upsample_steps <= pn_hier_max_samples(), num_steps >= 1, and >= 3 when
+ * upsample_steps > 0 (else PN_ERR_ARG).  half must be 0: there is no autocast form of this launch.  Results are a pure function of the ray (fixed summation
+ * order): they do not depend on N or on the order of the rays.  No host synchronisation, no allocation: legal inside a HIP-graph capture. */
+int pn_render_hier(const pn_net* net, const float* rays_o, const float* rays_d, uint32_t N, const float* aabb_host, float min_near, int num_steps,
+                   int upsample_steps, float density_scale, float bg_scalar, const float* bg_rays, float* image, float* depth, float* weights_sum, int half,
+                   void* stream);
+/* [host] largest num_steps + upsample_steps pn_render_hier takes. */
+int pn_hier_max_samples(void);
+
 /* ------------------------------------------------------------------ whole frame ---- */
 
 /* NeRFRenderer.rund_cuda (nerf/renderer.py:755-907) for one frame with no host synchronisation inside the loop:

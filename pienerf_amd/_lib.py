@@ -73,6 +73,10 @@ SIGNATURES = {
     "pn_background_forward": (i32, [P, P, P, u32, f32, P, P, P, P, P]),
     "pn_background_forward_half": (i32, [P, P, P, u32, f32, P, P, P, P, P]),
     "pn_background_coords": (i32, [P, P, P, u32, P, i32, P]),
+    "pn_nerf_color": (i32, [P, P, P, P, u32, P, P]),
+    "pn_nerf_color_half": (i32, [P, P, P, P, u32, P, P]),
+    "pn_render_hier": (i32, [P, P, P, u32, C.POINTER(f32), f32, i32, i32, f32, f32, P, P, P, P, i32, P]),
+    "pn_hier_max_samples": (i32, []),
     "pn_frame_create": (i32, [C.POINTER(P), u32, u32, u32]),
     "pn_frame_destroy": (None, [P]),
     "pn_render_deformed": (i32, [P, P, C.POINTER(RenderOpts), P, P, u32, P, P, P, P, i32, P, P, P, P, P, P, P]),

@@ -35,6 +35,10 @@ UNITS = {
     "pn_encoder_grad.hip": ["-ffp-contract=fast"],
     "pn_grid_nd.hip": ["-ffp-contract=fast"],
     "pn_background.hip": ["-ffp-contract=off"],  # shares pn_sph.h with pn_render_ops.hip (the coordinate bit for bit) and blends with two roundings; the network tile contracts inside itself
+    # NeRFRenderer.run fused + the masked colour query: the ray-side arithmetic (z, positions, deltas, alpha, the cdf's interpolation, the blend's two
+    # roundings) rounds once per operation like the torch op sequence it restates (run_ops); tolerance work, so this is a choice of the closer restatement,
+    # not a bit-exactness requirement.  The network tile contracts inside itself.
+    "pn_hier.hip": ["-ffp-contract=off"],
     "pn_sim.hip": ["-ffp-contract=fast"],
     "pn_drag.hip": ["-ffp-contract=fast"],   # shares pn_sim_ip.h with pn_sim.hip: the same contraction, the same bits
     "pn_mesh.hip": ["-ffp-contract=off"],  # marching cubes: the vertex formula rounds as written (tests/mc_reference.py restates it bit for bit)

@@ -177,6 +177,46 @@ class NeRFNetwork(NeRFRenderer):
         check(lib().pn_nerf_density(self._net_handle(), ptr(x), M, ptr(sigma), ptr(geo), stream_ptr()), "nerf_density")
         return {"sigma": sigma, "geo_feat": geo}
 
+    def color(self, x, d, mask=None, geo_feat=None, **kwargs):
+        """NeRFNetwork.color (nerf/network.py:165-194): the colour net on [SH(d) | geo_feat], on the rows where `mask` is set only; the other rows are
+        exact zeros.  x [N,3] is not used (nor is it in the reference); mask [N] bool or None (every row); geo_feat [N,15] from ``density``.
+        With autograd recording in train() mode: the reference's torch ops.  Otherwise one launch (pn_nerf_color) that compacts the masked rows into
+        32-row tiles; under fp16 autocast its half form.  Returns float32 [N,3] with a mask (half colours written into a float tensor, :190) and the
+        colour net's own output without one (a half tensor under autocast)."""
+        if self._wants_grad(x, d):
+            rgbs = None
+            if mask is not None:
+                rgbs = torch.zeros(mask.shape[0], 3, dtype=x.dtype, device=x.device)
+                if not mask.any():
+                    return rgbs
+                d, geo_feat = d[mask], geo_feat[mask]
+            h = torch.cat([self.encoder_dir(d), geo_feat], dim=-1)
+            for i, layer in enumerate(self.color_net):
+                h = layer(h)
+                if i != self.num_layers_color - 1:
+                    h = F.relu(h, inplace=True)
+            h = torch.sigmoid(h)
+            if mask is None:
+                return h
+            rgbs[mask] = h.to(rgbs.dtype)
+            return rgbs
+        if mask is not None and mask.numel() == 0:   # the result has one row per mask entry (num_steps = 1 hands over an empty mask)
+            return torch.zeros(0, 3, dtype=torch.float32, device=d.device)
+        d = d.to(torch.float32).contiguous().view(-1, 3)
+        geo = geo_feat.to(torch.float32).contiguous().view(-1, 15)
+        require_gpu(d, geo, mask)
+        M = d.shape[0]
+        assert geo.shape[0] == M
+        m8 = None
+        if mask is not None:
+            assert mask.dtype == torch.bool and mask.numel() == M
+            m8 = mask.contiguous().view(-1).view(torch.uint8)
+        rgbs = torch.empty(M, 3, dtype=torch.float32, device=d.device)
+        half = self._autocast_half()
+        fn = lib().pn_nerf_color_half if half else lib().pn_nerf_color
+        check(fn(self._net_handle(half=half), ptr(d), ptr(geo), ptr(m8), M, ptr(rgbs), stream_ptr()), "nerf_color")
+        return rgbs.to(torch.float16) if (half and mask is None) else rgbs
+
     def forward_ops(self, x, d):
         """The reference's op sequence: GridEncoder -> Linear/ReLU -> exp | SHEncoder, cat -> Linear/ReLU x3 -> sigmoid."""
         h = self.encoder(x, bound=self.bound)
@@ -261,7 +301,8 @@ class NeRFNetwork(NeRFRenderer):
             self.encoder.embeddings.copy_(torch.from_numpy(ck["embeddings"]).to(dev))
             for layer, key in zip(list(self.sigma_net) + list(self.color_net), ("W0", "W1", "W2", "W3", "W4")):
                 layer.weight.copy_(torch.from_numpy(ck[key]).to(dev))
-            self.density_bitfield.copy_(torch.from_numpy(ck["density_bitfield"]).to(dev))
+            if self.cuda_ray:   # a model without the density grid has no such buffer (renderer.py:101-106)
+                self.density_bitfield.copy_(torch.from_numpy(ck["density_bitfield"]).to(dev))
             if self.bg_net is not None and "bg_embeddings" in ck:   # make_checkpoint(..., bg_radius=R): encoder_bg.embeddings, bg_net.{0,1}.weight
                 assert tuple(self.encoder_bg.offsets.cpu().numpy()) == tuple(np.asarray(ck["bg_offsets"])), "background grid geometry mismatch"
                 self.encoder_bg.embeddings.copy_(torch.from_numpy(ck["bg_embeddings"]).to(dev))

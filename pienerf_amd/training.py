@@ -91,7 +91,7 @@ class Trainer:
         self.ema = ParamEMA(model.parameters(), ema_decay) if ema_decay is not None else None
 
     def _render_opts(self):
-        keep = ("dt_gamma", "max_steps", "T_thresh")
+        keep = ("dt_gamma", "max_steps", "T_thresh", "num_steps", "upsample_steps")   # the last two: the sampler of a model without cuda_ray (get_opts.py:19-22)
         return {k: self.opt[k] for k in keep if k in self.opt}
 
     def train_step(self, data):
