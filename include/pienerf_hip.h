@@ -585,6 +585,28 @@ int pn_mc_emit(const float* field, int nx, int ny, int nz, double threshold, con
 /* [host] The case table the kernels use: tri_count [256], tri_edges [256*15] (Bourke edge ids, -1 padded).  No GPU needed. */
 int pn_mc_case_table(uint8_t* tri_count, int8_t* tri_edges);
 
+/* ------------------------------------------------------------------ training data ---- */
+
+/* The data side of a training step (csrc/pn_train_batch.hip, INTEGRATION.md "Training data").  Random numbers are inputs drawn by the caller, so each
+ * entry is a pure function of its arguments. */
+
+/* Weighted sampling without replacement, for torch.multinomial(error_map, N, replacement=False) (nerf/utils.py:106).  weights [n_cells] fp32 >= 0,
+ * n_cells <= 16384; expo [n_cells]: Exp(1) draws.  cells_out [N] int64: the N cells with the largest keys weights[i] / expo[i] (IEEE division), in
+ * ascending cell index; a tie at the N-th key goes to the lower index; a cell of weight zero is never returned.  *status (device int) = 0, or 1 when
+ * fewer than N weights are positive (cells_out is then not written).  One workgroup, no atomics: equal inputs give equal bytes. */
+int pn_sample_cells(const float* weights, const float* expo, int n_cells, int N, int64_t* cells_out, int* status, void* stream);
+/* get_rays with N > 0 for one pose (nerf/utils.py:77-136) and the gather of the ground truth (nerf/provider.py:311-316), one launch.
+ * pose: device, row-major 4x4 cam2world.  mode 0 (:101): a [N] = pixel indices.  mode 1 (:106-115): a [N] = coarse cells of the 128 x 128 error
+ * map, u [2, N] uniforms in [0, 1).  mode 2 (:81-98): a, b [N / patch^2] = top-left rows / columns of the patches, pixels patch-major, then patch
+ * row, then patch column.  Writes inds_out [N] int64 (row * W + col), rays_o / rays_d [N, 3] — a pixel's direction is bit for bit pn_get_rays' —
+ * and, when `image` [H, W, C] fp32 (C = 3 or 4) is given, pixels_out [N, C] = image[inds].  a, b: int64. */
+int pn_train_batch(const float* pose, float fx, float fy, float cx, float cy, int H, int W, int N, int mode, const int64_t* a, const int64_t* b,
+                   const float* u, int patch, const float* image, int C, int64_t* inds_out, float* rays_o, float* rays_d, float* pixels_out,
+                   void* stream);
+/* The error map's moving average (nerf/trainer.py:239-243): map_row[cells[i]] = 0.1f * map_row[cells[i]] + 0.9f * err[i], i < N; map_row [128 * 128]
+ * is the row of the batch's view, cells [N] int64 are distinct. */
+int pn_error_map_update(float* map_row, const int64_t* cells, const float* err, int N, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

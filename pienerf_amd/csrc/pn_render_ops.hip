@@ -3,6 +3,7 @@
 #include <float.h>
 
 #include "pn_march_window.h"
+#include "pn_ray_dir.h"
 #include "pn_sph.h"
 
 thread_local char pn_err_buf[512] = {0};
@@ -140,15 +141,7 @@ __global__ void __launch_bounds__(256) k_get_rays(const float* __restrict__ pose
                                                   float* __restrict__ rays_o, float* __restrict__ rays_d) {
     const int p = threadIdx.x + blockIdx.x * blockDim.x;
     if (p >= HW) return;
-    const float i = (float)(p % W) + 0.5f, j = (float)(p / W) + 0.5f;
-    const float xs = (i - cx) / fx, ys = (j - cy) / fy, zs = 1.0f;
-    const float nrm = sqrtf(xs * xs + ys * ys + zs * zs);
-    const float d0 = xs / nrm, d1 = ys / nrm, d2 = zs / nrm;
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        rays_d[p * 3 + c] = d0 * pose[c * 4] + d1 * pose[c * 4 + 1] + d2 * pose[c * 4 + 2];
-        rays_o[p * 3 + c] = pose[c * 4 + 3];
-    }
+    pn_pixel_ray(pose, fx, fy, cx, cy, p % W, p / W, rays_o + p * 3, rays_d + p * 3);  // pn_ray_dir.h, shared with the training batch
 }
 
 extern "C" int pn_get_rays(const float* pose, float fx, float fy, float cx, float cy, int H, int W, float* rays_o, float* rays_d, void* stream) {

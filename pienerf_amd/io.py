@@ -71,9 +71,9 @@ def _safe_load(path, map_location, allow_pickle):
 
 
 def load_checkpoint(model, path, model_only=True, optimizer=None, lr_scheduler=None, map_location=None, ema=None, allow_pickle=False, scaler=None):
-    """trainer.py:856-916.  Returns dict(missing_keys, unexpected_keys, epoch, global_step).  The model is left in eval() mode."""
+    """trainer.py:856-916.  Returns dict(missing_keys, unexpected_keys, epoch, global_step, stats).  The model is left in eval() mode."""
     ck = _safe_load(path, map_location or next(model.parameters()).device, allow_pickle)
-    info = dict(missing_keys=[], unexpected_keys=[], epoch=None, global_step=None)
+    info = dict(missing_keys=[], unexpected_keys=[], epoch=None, global_step=None, stats=None)
     if "model" not in ck:  # a bare state dict
         model.load_state_dict(ck)
     else:
@@ -85,7 +85,7 @@ def load_checkpoint(model, path, model_only=True, optimizer=None, lr_scheduler=N
             if "mean_density" in ck:
                 model.mean_density = ck["mean_density"]
         if not model_only:
-            info["epoch"], info["global_step"] = ck.get("epoch"), ck.get("global_step")
+            info["epoch"], info["global_step"], info["stats"] = ck.get("epoch"), ck.get("global_step"), ck.get("stats")
             if optimizer is not None and "optimizer" in ck:
                 optimizer.load_state_dict(ck["optimizer"])
             if lr_scheduler is not None and "lr_scheduler" in ck:

@@ -6,12 +6,18 @@ Reference: main_train.py:60-80 (Adam(get_params(lr), betas=(0.9, 0.99), eps=1e-1
 ``update_extra_interval`` steps, zero_grad / backward / step / scheduler per step).  Data comes as posed images already on the device
 (there is no dataset on the box): ``RayImageSet`` samples ``num_rays`` random pixels of a random view per step like
 nerf/provider.py's training collate (one view per batch, rays drawn uniformly, :270-300).
+
+Training from images on disk (``pienerf_amd.main_train``): ``Trainer.fit`` runs epochs over a ``NeRFDataset`` loader (nerf/provider.py), writes the
+per-epoch checkpoints ``main_render --ckpt`` looks for and evaluates on a second loader; ``Trainer.evaluate_loader`` is the reference's
+``evaluate_one_epoch``.  Reference: nerf/trainer.py:224-246 (error map), :382-406 (train), :689-792 (evaluate_one_epoch), :794-830 (save_checkpoint).
 """
 import os
 
+import numpy as np
 import torch
 
-from .nerf.utils import extract_geometry, get_rays, write_to_ply
+from . import io
+from .nerf.utils import error_map_update, extract_geometry, get_rays, write_to_ply
 
 
 class RayImageSet:
@@ -75,9 +81,22 @@ class ParamEMA:
             s.copy_(v.to(s.device))
 
 
+class _LoaderFeed:
+    """One pass over a data loader behind ``RayImageSet``'s ``batch`` interface: Trainer.fit runs its epochs through Trainer.train."""
+
+    def __init__(self, loader):
+        self.batches = iter(loader)
+
+    def batch(self, num_rays):  # the loader's data set has sampled its own num_rays
+        return next(self.batches)
+
+
 class Trainer:
-    def __init__(self, model, opt, lr=1e-2, iters=30000, update_extra_interval=16, num_rays=4096, ema_decay=None, fp16=False):
-        """ema_decay: main_train.py:78 passes 0.95; None (default) trains without an average, like Trainer's own default (trainer.py:19).
+    def __init__(self, model, opt, lr=1e-2, iters=30000, update_extra_interval=16, num_rays=4096, ema_decay=None, fp16=False, name="ngp",
+                 eval_interval=50, max_keep_ckpt=2):
+        """opt: the render options of a step (dt_gamma, max_steps, T_thresh, ...) and, for ``fit`` / ``evaluate_loader``, ``color_space`` and
+        ``patch_size``.  name, eval_interval, max_keep_ckpt: trainer.py:17-31, used by ``fit``.
+        ema_decay: main_train.py:78 passes 0.95; None (default) trains without an average, like Trainer's own default (trainer.py:19).
         fp16 (trainer.py:20,84: ``--fp16``): the steps run under autocast with a GradScaler — half hash tables, half nn.Linear, and the half
         scatter-add of the grid's backward (gridencoder.cu:324-331)."""
         self.model, self.opt = model, dict(opt)
@@ -89,6 +108,9 @@ class Trainer:
         self.update_extra_interval, self.num_rays = update_extra_interval, num_rays
         self.global_step = 0
         self.ema = ParamEMA(model.parameters(), ema_decay) if ema_decay is not None else None
+        self.name, self.eval_interval, self.max_keep_ckpt = name, int(eval_interval), int(max_keep_ckpt)
+        self.epoch, self.workspace, self.error_map = 0, None, None   # error_map: the data set's, set by fit (trainer.py:391)
+        self.stats = {"loss": [], "valid_loss": [], "results": [], "checkpoints": [], "best_result": None}   # trainer.py:92-98
 
     def _render_opts(self):
         keep = ("dt_gamma", "max_steps", "T_thresh", "num_steps", "upsample_steps")   # the last two: the sampler of a model without cuda_ray (get_opts.py:19-22)
@@ -106,9 +128,13 @@ class Trainer:
             bg, gt_rgb = 1, images[..., :3] * images[..., 3:] + (1 - images[..., 3:])
         else:
             bg, gt_rgb = 1, images
-        outputs = self.model.render(data["rays_o"], data["rays_d"], staged=False, bg_color=bg, perturb=True, force_all_rays=False, **self._render_opts())
+        all_rays = int(self.opt.get("patch_size", 1)) != 1   # patches are rendered whole (trainer.py:201); their LPIPS term (:218) is not built
+        outputs = self.model.render(data["rays_o"], data["rays_d"], staged=False, bg_color=bg, perturb=True, force_all_rays=all_rays, **self._render_opts())
         pred_rgb = outputs["image"]
-        loss = self.criterion(pred_rgb, gt_rgb).mean(-1).mean()
+        loss = self.criterion(pred_rgb, gt_rgb).mean(-1)   # per ray [1, N]
+        if self.error_map is not None and "inds_coarse" in data:   # trainer.py:224-246: the sampled cells' moving average of the per-ray loss
+            error_map_update(self.error_map[int(data["index"][0])], data["inds_coarse"], loss)
+        loss = loss.mean()
         return pred_rgb, gt_rgb, loss
 
     def train(self, dataset, steps):
@@ -147,6 +173,86 @@ class Trainer:
         gt = img[..., :3] * img[..., 3:] + (1 - img[..., 3:]) if img.shape[-1] == 4 else img
         mse = torch.mean((out["image"].view(dataset.H, dataset.W, 3) - gt) ** 2)
         return float(-10 * torch.log10(mse)), out
+
+    # ------------------------------------------------------------------ epochs over a data loader (trainer.py:382-406)
+    def checkpoint_dir(self, workspace=None):
+        return os.path.join(workspace if workspace is not None else self.workspace, "checkpoints")
+
+    def save_checkpoint(self, workspace=None):
+        """trainer.py:794-830 (full=True, best=False, remove_old=True): ``checkpoints/{name}_ep%04d.pth`` with the optimiser, scheduler, scaler and
+        EMA state; the oldest file beyond ``max_keep_ckpt`` is removed."""
+        path = os.path.join(self.checkpoint_dir(workspace), f"{self.name}_ep{self.epoch:04d}.pth")
+        self.stats["checkpoints"].append(path)
+        if len(self.stats["checkpoints"]) > self.max_keep_ckpt:
+            old = self.stats["checkpoints"].pop(0)
+            if os.path.exists(old):
+                os.remove(old)
+        return io.save_checkpoint(self.model, path, epoch=self.epoch, global_step=self.global_step, stats=self.stats, optimizer=self.optimizer,
+                                  lr_scheduler=self.lr_scheduler, full=True, ema=self.ema, scaler=self.scaler)
+
+    def resume(self, path, allow_pickle=False):
+        """trainer.py:856-916 (model_only=False): model, optimiser, scheduler, scaler, EMA, epoch, global_step and stats of a full checkpoint."""
+        info = io.load_checkpoint(self.model, path, model_only=False, optimizer=self.optimizer, lr_scheduler=self.lr_scheduler, ema=self.ema,
+                                  scaler=self.scaler, allow_pickle=allow_pickle)
+        if info["epoch"] is not None:
+            self.epoch = int(info["epoch"])
+        if info["global_step"] is not None:
+            self.global_step = int(info["global_step"])
+        if isinstance(info.get("stats"), dict):
+            self.stats.update(info["stats"])
+        return info
+
+    def fit(self, train_loader, valid_loader, max_epochs, workspace):
+        """Trainer.train of the reference (trainer.py:382-406): the density cells no training camera sees are marked, then per epoch one pass over
+        ``train_loader`` through ``train``'s step code, a full checkpoint, and every ``eval_interval`` epochs ``evaluate_loader(valid_loader)``.
+        Starts behind ``self.epoch`` (``resume``).  Returns the per-step losses of the epochs it ran."""
+        self.workspace = workspace
+        data = train_loader._data
+        if self.model.cuda_ray:
+            self.model.mark_untrained_grid(data.poses, data.intrinsics)
+        self.error_map = data.error_map
+        losses = []
+        for epoch in range(self.epoch + 1, int(max_epochs) + 1):
+            self.epoch = epoch
+            epoch_losses = self.train(_LoaderFeed(train_loader), len(train_loader))
+            self.stats["loss"].append(sum(epoch_losses) / max(len(epoch_losses), 1))
+            losses += epoch_losses
+            self.save_checkpoint()
+            if self.epoch % self.eval_interval == 0 and valid_loader is not None:
+                self.evaluate_loader(valid_loader)
+        return losses
+
+    @torch.no_grad()
+    def evaluate_loader(self, loader, name=None):
+        """evaluate_one_epoch (trainer.py:689-792) with the PSNR meter: every view of ``loader`` rendered in eval() mode on the averaged weights against
+        its ground truth over white; the predictions go to ``{workspace}/validation/{name}_{i:04d}.png`` (through linear_to_srgb when the colour space
+        is linear).  Returns {'loss': mean MSE, 'psnr': mean PSNR} and records them in stats['valid_loss'] / stats['results']."""
+        name = name if name is not None else f"{self.name}_ep{self.epoch:04d}"
+        self.model.eval()
+        if self.ema is not None:
+            self.ema.store()
+            self.ema.copy_to()
+        total_loss, total_psnr, n = 0.0, 0.0, 0
+        for data in loader:
+            n += 1
+            images = data["images"]   # [1, H, W, C]
+            H, W = images.shape[1:3]
+            gt = images[..., :3] * images[..., 3:] + (1 - images[..., 3:]) if images.shape[-1] == 4 else images
+            with torch.autocast("cuda", dtype=torch.float16, enabled=self.fp16):   # trainer.py:716
+                out = self.model.render(data["rays_o"], data["rays_d"], staged=True, bg_color=1, perturb=False, **self._render_opts())
+            pred = out["image"].reshape(1, H, W, 3).to(torch.float32)
+            mse = float(torch.mean((pred - gt) ** 2))
+            total_loss += mse
+            total_psnr += -10 * float(np.log10(mse))   # PSNRMeter (nerf/utils.py:249-256)
+            if self.workspace is not None:
+                shown = io.linear_to_srgb(pred) if self.opt.get("color_space", "srgb") == "linear" else pred
+                io.save_image(shown[0], os.path.join(self.workspace, "validation", f"{name}_{n:04d}.png"), W, H)
+        if self.ema is not None:
+            self.ema.restore()
+        result = {"loss": total_loss / max(n, 1), "psnr": total_psnr / max(n, 1)}
+        self.stats["valid_loss"].append(result["loss"])
+        self.stats["results"].append(result["psnr"])
+        return result
 
     def _geometry(self, resolution, threshold):
         from .mesh import density_query
