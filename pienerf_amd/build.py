@@ -29,12 +29,15 @@ COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fhip-fp32-co
 # decisions vs the CPU oracle); the encoder/MLP and the fp64 simulator let the compiler contract to FMA.
 UNITS = {
     "pn_render_ops.hip": ["-ffp-contract=off"],
+    # the stand-alone ray ops: near/far and the static march share their arithmetic with pn_render_ops.hip (pn_near_far.h, pn_march_static.h), get_rays
+    # with pn_train_batch.hip (pn_ray_dir.h) and sph_from_ray with pn_background.hip (pn_sph.h), bit for bit
+    "pn_ray_ops.hip": ["-ffp-contract=off"],
     "pn_train_ops.hip": ["-ffp-contract=off"],
     "pn_grid_state.hip": ["-ffp-contract=off"],
     "pn_nerf_forward.hip": ["-ffp-contract=fast"],
     "pn_encoder_grad.hip": ["-ffp-contract=fast"],
     "pn_grid_nd.hip": ["-ffp-contract=fast"],
-    "pn_background.hip": ["-ffp-contract=off"],  # shares pn_sph.h with pn_render_ops.hip (the coordinate bit for bit) and blends with two roundings; the network tile contracts inside itself
+    "pn_background.hip": ["-ffp-contract=off"],  # shares pn_sph.h with pn_ray_ops.hip (the coordinate bit for bit) and blends with two roundings; the network tile contracts inside itself
     # NeRFRenderer.run fused + the masked colour query: the ray-side arithmetic (z, positions, deltas, alpha, the cdf's interpolation, the blend's two
     # roundings) rounds once per operation like the torch op sequence it restates (run_ops); tolerance work, so this is a choice of the closer restatement,
     # not a bit-exactness requirement.  The network tile contracts inside itself.
@@ -43,7 +46,7 @@ UNITS = {
     "pn_drag.hip": ["-ffp-contract=fast"],   # shares pn_sim_ip.h with pn_sim.hip: the same contraction, the same bits
     "pn_mesh.hip": ["-ffp-contract=off"],  # marching cubes: the vertex formula rounds as written (tests/mc_reference.py restates it bit for bit)
     # training batches: the pixel index restates separate torch ops (one rounding each), the keys of the weighted sampler are IEEE quotients, and a
-    # pixel's ray is pn_ray_dir.h's, shared with pn_render_ops.hip bit for bit
+    # pixel's ray is pn_ray_dir.h's, shared with pn_ray_ops.hip bit for bit
     "pn_train_batch.hip": ["-ffp-contract=off"],
     "pn_copier.hip": [],  # host code only: frame copies through the HSA runtime (links libhsa-runtime64)
 }

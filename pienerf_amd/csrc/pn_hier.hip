@@ -159,7 +159,7 @@ k_render_hier(const PnByteLevel* __restrict__ lv, const float* __restrict__ emb,
         const float ox = rays_o[ray * 3], oy = rays_o[ray * 3 + 1], oz = rays_o[ray * 3 + 2];
         const float dx = rays_d[ray * 3], dy = rays_d[ray * 3 + 1], dz = rays_d[ray * 3 + 2];
         float near, far;
-        {   // kernel_near_far_from_aabb (raymarching.cu:91-159; pn_render_ops.hip: k_near_far)
+        {   // kernel_near_far_from_aabb (raymarching.cu:91-159; pn_near_far.h restates the same for k_near_far and the frame prologue)
             const float rdx = 1 / dx, rdy = 1 / dy, rdz = 1 / dz;
             near = (aabb.v[0] - ox) * rdx; far = (aabb.v[3] - ox) * rdx;
             if (near > far) { const float c = near; near = far; far = c; }

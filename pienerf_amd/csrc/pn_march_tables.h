@@ -1,7 +1,7 @@
 // Side tables and per-point helpers of the ray march (gfx950): the candidate lists, the packed IP records, the Newton inverse
 // warp through one record.  The march itself (windows, skip pre-pass) is in pn_march_window.h.
 //
-// Per-frame side tables (built by k_frame_lists / k_nb_* + k_pack_ip in pn_render_ops.hip):
+// Per-frame side tables (built by k_frame_prologue in pn_frame_kernels.h / k_nb_* + k_pack_ip in pn_side_tables.h):
 //   nb_rng[n_grid], nb[...]    per cell (begin, end) of: the candidates of its 27-cell neighbourhood as float4(p_def.xyz, bitcast id), in the
 //                              reference's visiting order (own cell first, then NBR26; own-cell order = ascending id), so
 //                              "position in the list" is "visiting order" and ties resolve exactly as the sequential scan does

@@ -11,7 +11,7 @@
 // v_readlane).  Visited lanes that found an occupied sample write it to the slot given by their rank in the chain.  The round loop is
 // wave-uniform: the candidate lists and IP record heads the wave's points need are staged cooperatively in LDS (stage_lists, head_fetch).
 //
-// Two launches per loop trip use it (pn_render_ops.hip):
+// Two launches per loop trip use it (pn_march_kernels.h):
 //   k_march       G = 8, 8 rays per wave, at most `max_rounds` rounds per ray (2 on a frame's first trip, 1 afterwards): a ray in a
 //                 sample-dense region emits its 8 samples in one round.  Rays that are still going after the budget (they graze the
 //                 object or have left it and hop through 60-90 voxels without emitting) are appended to a segmented tail list with
@@ -133,7 +133,7 @@ __device__ __forceinline__ bool ray_start(const MarchParams& a, const RayConsts&
 // Where a ray can stop.  A sample is only ever emitted at a point whose search cell has candidates, so beyond the last such cell on its way
 // a ray does nothing but hop from voxel to voxel until `far` — for a ray that misses the object but crosses its bounding box that is ALL it
 // does (most of k_march_skip's work), and a ray that has left the object behind walks on through the tail pass (the longest tail rays).
-// `bits2` marks the cells within one cell of a cell with candidates (k_frame_lists); the ray is sampled backwards from `far` every 0.9 cell
+// `bits2` marks the cells within one cell of a cell with candidates (k_frame_prologue); the ray is sampled backwards from `far` every 0.9 cell
 // lengths, and the march may end at the last sample before the first marked one: any point beyond it lies within one cell (per axis) of an
 // unmarked sample, hence in a cell without candidates — with a whole cell to spare for the rounding of the reference's own cell arithmetic.
 // Returns `near` when no sample is marked (nothing to march).  Not for --cut (static samples need no candidates).

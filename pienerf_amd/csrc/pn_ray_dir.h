@@ -1,4 +1,4 @@
-// The direction and origin of one pixel's ray (nerf/utils.py:125-133), shared by k_get_rays (pn_render_ops.hip: every pixel of a view) and
+// The direction and origin of one pixel's ray (nerf/utils.py:125-133), shared by k_get_rays (pn_ray_ops.hip: every pixel of a view) and
 // k_train_batch (pn_train_batch.hip: the sampled pixels of a training step).  Both units are built with -ffp-contract=off, so the two kernels
 // write the same bits for the same pixel.
 #pragma once

@@ -1,6 +1,6 @@
 // Where a ray leaves the sphere of `radius` (the larger root), as (theta, phi) scaled to [-1, 1]: kernel_sph_from_ray, raymarching.cu:165-202 — the texture
 // coordinate of the background model (renderer.py:246, bg_radius > 0).  atan2f / sqrtf of the device library, like the reference.  ONE body for the
-// stand-alone op (pn_render_ops.hip: k_sph_from_ray) and the fused background kernel (pn_background.hip): both translation units are built with
+// stand-alone op (pn_ray_ops.hip: k_sph_from_ray) and the fused background kernel (pn_background.hip): both translation units are built with
 // -ffp-contract=off, so the two run the same instructions and the coordinates agree bit for bit (tests/test_gpu_background.py).
 #pragma once
 

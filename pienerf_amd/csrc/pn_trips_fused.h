@@ -1,4 +1,4 @@
-// Every loop trip after the first ones of a deformed frame as ONE launch (gfx950).  Included by pn_render_ops.hip behind composite_one / pn_frame.
+// Every loop trip after the first ones of a deformed frame as ONE launch (gfx950).  Included by pn_frame_kernels.h (the render unit, pn_render_ops.hip) behind the trip kernels and composite_one.
 //
 // The reference's render loop (nerf/renderer.py:836-891) is, per trip: march n_step samples for every alive ray -> network on all samples -> composite
 // -> rays_alive = rays_alive[rays_alive >= 0], with n_step = max(min(N // n_alive, 8), 1).  Rounds 1-3 ran that as 4-6 launches per trip (march pass,

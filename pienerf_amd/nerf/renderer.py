@@ -21,6 +21,11 @@ from .._lib import RenderOpts, check, lib, ptr, require_gpu, stream_ptr
 from .utils import get_pnts_in_grids
 
 
+def _flat_rays(rays_o, rays_d):
+    """The rays as the frame drivers take them: [N, 3], fp32, contiguous."""
+    return rays_o.to(torch.float32).contiguous().view(-1, 3), rays_d.to(torch.float32).contiguous().view(-1, 3)
+
+
 def sample_pdf(bins, weights, n_samples, det=False):
     """nerf/renderer.py:19-53 (the original NeRF's inverse-CDF sampling), torch ops on whatever device the inputs live on.
     bins [B, T] (the old z values), weights [B, T - 1] (bin weights) -> [B, n_samples] new z values; det: the midpoints of n_samples equal
@@ -164,12 +169,20 @@ class NeRFRenderer(nn.Module):
         o.fused_whole = int(bool(kwargs.get("fused_whole")))  # extension: ... the frame's first trip included, where it applies (pn_render_opts.fused_whole)
         return o
 
+    def _static_opts(self, dt_gamma, bg_scalar, max_steps, T_thresh):
+        """The option set of the static render (pn_render_static, and pn_render_continue on a static frame): no IP state, no ray groups, no fused launch."""
+        o = RenderOpts()
+        o.max_iter_num, o.hash_grid_size, o.num_seek_IP, o.IP_dx, o.cut = 1, 1.0, 1, 0.0, 0
+        o.bound, o.min_near, o.dt_gamma, o.max_steps, o.T_thresh = float(self.bound), float(self.min_near), float(dt_gamma), int(max_steps), float(T_thresh)
+        o.cascade, o.grid_size, o.density_scale, o.bg_color = int(self.cascade), int(self.grid_size), float(self.density_scale), float(bg_scalar)
+        o.fp16 = int(self._autocast_half())
+        return o
+
     def rund_cuda(self, rays_o, rays_d, dt_gamma=0, bg_color=None, perturb=False, max_steps=1024, T_thresh=1e-2, **kwargs):
         if perturb:
             return self.rund_cuda_ops(rays_o, rays_d, dt_gamma, bg_color, perturb, max_steps, T_thresh, **kwargs)
         prefix = rays_o.shape[:-1]
-        rays_o = rays_o.to(torch.float32).contiguous().view(-1, 3)
-        rays_d = rays_d.to(torch.float32).contiguous().view(-1, 3)
+        rays_o, rays_d = _flat_rays(rays_o, rays_d)
         require_gpu(rays_o, rays_d)
         N, device = rays_o.shape[0], rays_o.device
         if self.bg_radius > 0:
@@ -219,17 +232,12 @@ class NeRFRenderer(nn.Module):
         SAME output tensors `out` (the dict the render returned).  The reference's loop has no trip limit but max_steps (renderer.py:836-891);
         this is how the captured, fixed-length forms keep that semantics.  Blocking when n_trips == 0.  With a background model the epilogue
         composites over 0 again and the model's colour is blended in again, once."""
-        rays_o = rays_o.to(torch.float32).contiguous().view(-1, 3)
-        rays_d = rays_d.to(torch.float32).contiguous().view(-1, 3)
+        rays_o, rays_d = _flat_rays(rays_o, rays_d)
         N = rays_o.shape[0]
         if self.bg_radius > 0:
             bg_color = 0
         if static:
-            o = RenderOpts()
-            o.max_iter_num, o.hash_grid_size, o.num_seek_IP, o.IP_dx, o.cut = 1, 1.0, 1, 0.0, 0
-            o.bound, o.min_near, o.dt_gamma, o.max_steps, o.T_thresh = float(self.bound), float(self.min_near), float(dt_gamma), int(max_steps), float(T_thresh)
-            o.cascade, o.grid_size, o.density_scale, o.bg_color = int(self.cascade), int(self.grid_size), float(self.density_scale), float(1 if bg_color is None else bg_color)
-            o.fp16 = int(self._autocast_half())
+            o = self._static_opts(dt_gamma, 1 if bg_color is None else bg_color, max_steps, T_thresh)
         else:
             o = self._deformed_opts(dt_gamma, 1 if bg_color is None else bg_color, max_steps, T_thresh, kwargs, n_rays=N)
         image, depth, ws = out["image"].view(-1, 3), out["depth"].view(-1), out["weights_sum"].view(-1)
@@ -319,17 +327,12 @@ class NeRFRenderer(nn.Module):
 
     def _run_static_fused(self, rays_o, rays_d, dt_gamma, bg_color, max_steps, T_thresh, **kwargs):
         prefix = rays_o.shape[:-1]
-        rays_o = rays_o.to(torch.float32).contiguous().view(-1, 3)
-        rays_d = rays_d.to(torch.float32).contiguous().view(-1, 3)
+        rays_o, rays_d = _flat_rays(rays_o, rays_d)
         require_gpu(rays_o, rays_d)
         if self.bg_radius > 0:
             bg_color = 0   # renderer.py:283-288: the model's colour, blended in below
         N, device = rays_o.shape[0], rays_o.device
-        o = RenderOpts()
-        o.max_iter_num, o.hash_grid_size, o.num_seek_IP, o.IP_dx, o.cut = 1, 1.0, 1, 0.0, 0
-        o.bound, o.min_near, o.dt_gamma, o.max_steps, o.T_thresh = float(self.bound), float(self.min_near), float(dt_gamma), int(max_steps), float(T_thresh)
-        o.cascade, o.grid_size, o.density_scale, o.bg_color = int(self.cascade), int(self.grid_size), float(self.density_scale), float(bg_color)
-        o.fp16 = int(self._autocast_half())
+        o = self._static_opts(dt_gamma, bg_color, max_steps, T_thresh)
         aabb = (C.c_float * 6)(*self._aabb_infer_host())
         image, depth, depth_0, ws = (torch.empty(N, 3, dtype=torch.float32, device=device), torch.empty(N, dtype=torch.float32, device=device),
                                      torch.empty(N, dtype=torch.float32, device=device), torch.empty(N, dtype=torch.float32, device=device))
@@ -453,8 +456,7 @@ class NeRFRenderer(nn.Module):
 
     def _run_hier_fused(self, rays_o, rays_d, num_steps, upsample_steps, bg_color):
         prefix = rays_o.shape[:-1]
-        rays_o = rays_o.to(torch.float32).contiguous().view(-1, 3)
-        rays_d = rays_d.to(torch.float32).contiguous().view(-1, 3)
+        rays_o, rays_d = _flat_rays(rays_o, rays_d)
         require_gpu(rays_o, rays_d)
         N, device = rays_o.shape[0], rays_o.device
         bg_rays, bg_scalar = None, 1.0

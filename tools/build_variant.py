@@ -15,7 +15,7 @@ out_dir = os.path.join(b.HERE, "lib", "variants")
 obj_dir = os.path.join(out_dir, "obj_" + name)
 os.makedirs(obj_dir, exist_ok=True)
 objs = []
-only = os.environ.get("PN_VARIANT_UNITS", "pn_render_ops.hip").split(",")  # the other units are taken from the base build
+only = os.environ.get("PN_VARIANT_UNITS", "pn_render_ops.hip").split(",")  # the render unit with its headers (pn_march_kernels.h, pn_trips_fused.h, ...: where the tuning macros live); the other units are taken from the base build
 b.build()
 for src, extra in b.UNITS.items():
     if src not in only:

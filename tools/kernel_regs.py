@@ -1,6 +1,9 @@
 """Register / spill / scratch summary of the kernels in a HIP translation unit (reads the code-object metadata of an -S dump).
 
     python tools/kernel_regs.py pienerf_amd/csrc/pn_render_ops.hip [name-filter]
+
+The unit is the .hip file: the render unit's kernels live in headers it includes (pn_march_kernels.h, pn_compact.h, pn_frame_kernels.h, ...), the
+stand-alone ray ops in pn_ray_ops.hip.
 """
 import re
 import subprocess
