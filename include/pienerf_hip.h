@@ -585,6 +585,15 @@ int pn_mc_emit(const float* field, int nx, int ny, int nz, double threshold, con
 /* [host] The case table the kernels use: tri_count [256], tri_edges [256*15] (Bourke edge ids, -1 padded).  No GPU needed. */
 int pn_mc_case_table(uint8_t* tri_count, int8_t* tri_edges);
 
+/* Connected-component labelling of an occupancy lattice (csrc/pn_components.hip, DESIGN.md 4.6, INTEGRATION.md "Connected components").  `occ` is a
+ * C-contiguous uint8 lattice [nx, ny, nz] (z fastest, pn_mc_count's layout), non-zero = occupied; `labels` is int32 of the same shape.  An occupied
+ * voxel receives the smallest flat index (i*ny + j)*nz + k of any voxel of its component, an empty voxel -1.  connectivity: 6 (faces) or 26 (faces,
+ * edges and corners).  PN_ERR_ARG for a null pointer, a side < 1, nx*ny*nz >= 2^31 or any other connectivity (checked before anything is enqueued).
+ * Three launches on `stream` whatever the data, no scratch memory (`labels` is the union-find's parent array), no allocation and no host
+ * synchronisation: legal inside a stream capture.  Integer atomicMin union-find hooking the larger root under the smaller: the labels are a pure
+ * function of `occ`. */
+int pn_ccl_label(const uint8_t* occ, int nx, int ny, int nz, int connectivity, int* labels, void* stream);
+
 /* ------------------------------------------------------------------ training data ---- */
 
 /* The data side of a training step (csrc/pn_train_batch.hip, INTEGRATION.md "Training data").  Random numbers are inputs drawn by the caller, so each

@@ -123,6 +123,7 @@ SIGNATURES = {
     "pn_mc_count": (i32, [P, i32, i32, i32, f64, P, P, P]),
     "pn_mc_emit": (i32, [P, i32, i32, i32, f64, P, P, P, P]),
     "pn_mc_case_table": (i32, [P, P]),
+    "pn_ccl_label": (i32, [P, i32, i32, i32, i32, P, P]),
     "pn_sample_cells": (i32, [P, P, i32, i32, P, P, P]),
     "pn_train_batch": (i32, [P, f32, f32, f32, f32, i32, i32, i32, i32, P, P, P, i32, P, i32, P, P, P, P, P]),
     "pn_error_map_update": (i32, [P, P, P, i32, P]),

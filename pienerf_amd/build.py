@@ -48,6 +48,7 @@ UNITS = {
     # training batches: the pixel index restates separate torch ops (one rounding each), the keys of the weighted sampler are IEEE quotients, and a
     # pixel's ray is pn_ray_dir.h's, shared with pn_ray_ops.hip bit for bit
     "pn_train_batch.hip": ["-ffp-contract=off"],
+    "pn_components.hip": ["-ffp-contract=off"],  # connected-component labelling: integers only, the flag has nothing to act on
     "pn_copier.hip": [],  # host code only: frame copies through the HSA runtime (links libhsa-runtime64)
 }
 

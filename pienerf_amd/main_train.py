@@ -68,6 +68,8 @@ def parser():
     # this front end's own
     ap.add_argument("--eval_interval", type=int, default=50, help="validate every this many epochs (the reference's main_train.py fixes 50)")
     ap.add_argument("--resolution", type=int, default=256, help="lattice resolution of the final point cloud / the --test mesh")
+    ap.add_argument("--con", dest="components", type=int, default=0, help="keep this many largest connected components of the density field in the final point cloud / the "
+                    "--test mesh; 0 (default) keeps all.  The reference declares --con with default 1 and never reads it, so off is the faithful default")
     ap.add_argument("--trust-ckpt", dest="trust_ckpt", action="store_true", help="allow a checkpoint that needs arbitrary pickle globals")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--quiet", action="store_true")
@@ -134,7 +136,7 @@ def run(opt):
             res["test"] = trainer.evaluate_loader(test_loader)
             say(f"test: {res['test']}")
         res["mesh"] = os.path.join(opt.workspace, "meshes", f"{trainer.name}_{trainer.epoch}.ply")
-        trainer.save_mesh(res["mesh"], resolution=opt.resolution, threshold=10)
+        trainer.save_mesh(res["mesh"], resolution=opt.resolution, threshold=10, components=opt.components)
         return res
     train_loader = NeRFDataset(opt, device=opt.device, type="train").dataloader()
     valid_loader = NeRFDataset(opt, device=opt.device, type="val", downscale=1).dataloader()
@@ -151,7 +153,7 @@ def run(opt):
         res["test"] = trainer.evaluate_loader(test_loader)
         say(f"test: {res['test']}")
     res["point_cloud"] = os.path.join(opt.workspace, "points", f"{trainer.name}_{trainer.epoch}.ply")
-    trainer.save_point_cloud(res["point_cloud"], resolution=opt.resolution, threshold=10)
+    trainer.save_point_cloud(res["point_cloud"], resolution=opt.resolution, threshold=10, components=opt.components)
     return res
 
 

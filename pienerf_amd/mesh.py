@@ -1,6 +1,6 @@
 """Marching cubes on the GPU and the density lattice it meshes (nerf/utils.py:174-205 of the reference: extract_fields + mcubes.marching_cubes).
 
-    python -m pienerf_amd.mesh --out DIR [--ckpt PATH] [--resolution 256] [--threshold 10] [--fp16]
+    python -m pienerf_amd.mesh --out DIR [--ckpt PATH] [--resolution 256] [--threshold 10] [--fp16] [--con N]
 
 writes DIR/mesh.ply (Trainer.save_mesh's file) and DIR/points.ply (save_point_cloud's) for a checkpoint; default: the synthetic chair whose density
 field has the solid's shape (scene.make_checkpoint(shaped=True)).
@@ -78,11 +78,7 @@ def density_query(model, fp16=False):
     return query
 
 
-def main(argv=None):
-    from . import io, scene
-    from .nerf.network import NeRFNetwork
-    from .nerf.utils import extract_geometry, write_to_ply
-
+def parser():
     ap = argparse.ArgumentParser(description="Mesh and surface point cloud of a density field (Trainer.save_mesh / save_point_cloud)")
     ap.add_argument("--out", default="output_mesh", help="directory for mesh.ply and points.ply")
     ap.add_argument("--ckpt", default=None, help="a reference-format .pth or a checkpoints directory; default: the shaped synthetic chair")
@@ -92,8 +88,18 @@ def main(argv=None):
     ap.add_argument("--fp16", action="store_true", help="query the density under autocast (Trainer(fp16=True))")
     ap.add_argument("--bound", type=float, default=1.0)
     ap.add_argument("--bg_radius", type=float, default=-1, help="> 0: the checkpoint holds a background model (its tensors are loaded; meshing does not use them)")
+    ap.add_argument("--con", dest="components", type=int, default=0, help="mesh only this many largest connected components of the above-threshold nodes; 0 (default) "
+                    "meshes everything.  The reference declares --con with default 1 and never reads it, so off is the faithful default")
     ap.add_argument("--device", default="cuda:0")
-    args = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None):
+    from . import io, scene
+    from .nerf.network import NeRFNetwork
+    from .nerf.utils import extract_geometry, write_to_ply
+
+    args = parser().parse_args(argv)
     model = NeRFNetwork(encoding="hashgrid", bound=args.bound, cuda_ray=True, density_scale=1, min_near=0.2, density_thresh=10, bg_radius=args.bg_radius)
     model = model.to(args.device)
     if args.ckpt:
@@ -108,7 +114,7 @@ def main(argv=None):
     query = density_query(model, args.fp16)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    vertices, triangles = extract_geometry(model.aabb_infer[:3], model.aabb_infer[3:], args.resolution, args.threshold, query)
+    vertices, triangles = extract_geometry(model.aabb_infer[:3], model.aabb_infer[3:], args.resolution, args.threshold, query, components=args.components)
     t1 = time.perf_counter()
     scene.write_mesh_ply(os.path.join(args.out, "mesh.ply"), vertices, triangles)
     t2 = time.perf_counter()

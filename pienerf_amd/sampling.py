@@ -15,6 +15,10 @@ lattice against a `2*bound/res` cell size).  Deliberate, documented differences 
     of points, reproducible order);
   * `get_point_volumes` (:182-200) loops over all hash cells on the host; here it is one gather.
 The uniform numbers of `torch.rand` (:268) can be passed in (`rand=`) so that a run is reproducible and testable.
+
+`con` > 0 (get_opts.py:72, "num of connected components to keep"; the reference declares it and `vres`, :71, and reads neither) drops floaters:
+the kept points are binned into a `vres`^3 occupancy lattice, the lattice is labelled on the GPU (components.py) and only the points of the `con`
+largest components survive.  0, the default, is off: the points and volumes are those of the code without the option, bit for bit.
 """
 import os
 
@@ -36,6 +40,9 @@ class AdaptiveUniformSampling:
         self.sub_coeff = float(opt.get("sub_coeff", 0.1))               # get_opts.py:78
         self.model = model.to(self.device)
         self.grid_size = 2 * self.bound / self.res                      # main_sample.py:155
+        self.con = int(opt.get("con", 0))                               # get_opts.py:72; 0: keep every component
+        self.vres = int(opt.get("vres", 96))                            # get_opts.py:71
+        self.con_connectivity = int(opt.get("con_connectivity", 26))
 
     # ------------------------------------------------------------------ main_sample.py:164-180
     def get_density(self, x):
@@ -89,6 +96,26 @@ class AdaptiveUniformSampling:
         vols[pig_idx.long()] = vol[cell_of_slot]
         return vols
 
+    # ------------------------------------------------------------------ the floater filter (`con` > 0)
+    def component_filter(self, pts):
+        """pts [n,3]: the points above the threshold -> (keep [n] bool, info).  A `vres`^3 lattice over [-bound, bound]^3, indexed [ix, iy, iz]; a
+        point's voxel is floor((p + bound) / (2 bound / vres)) clamped into the lattice.  A voxel is occupied when its centre is above the density
+        threshold OR a point lies in it (so every point sits in an occupied voxel, also when vres > sub_res); the points whose voxel belongs to one
+        of the `con` largest components are kept."""
+        from .components import count_components, label_components, select_components
+        vres, dev = self.vres, self.device
+        cell = 2 * self.bound / vres
+        c = (torch.arange(vres, dtype=torch.float32, device=dev) + 0.5) * cell - self.bound
+        centres = torch.stack(torch.meshgrid(c, c, c, indexing="ij"), dim=-1).reshape(-1, 3)
+        occ = self.get_density(centres) > self.threshold
+        vox = torch.floor((pts + self.bound) / cell).clamp_(0, vres - 1).long()
+        flat = (vox[:, 0] * vres + vox[:, 1]) * vres + vox[:, 2]
+        occ[flat] = True
+        labels = label_components(occ.view(vres, vres, vres), self.con_connectivity)
+        mask, kept = select_components(labels, self.con)
+        keep = mask.view(-1)[flat]
+        return keep, dict(components=count_components(labels), kept_components=kept, dropped_points=int((~keep).sum()))
+
     # ------------------------------------------------------------------ main_sample.py:202-308
     @torch.no_grad()
     def sample(self, rand=None, generator=None):
@@ -140,7 +167,11 @@ class AdaptiveUniformSampling:
         density = self.get_density(pts)
         pts = pts[density > self.threshold]
         assert pts.shape[0] > 0, "No points sampled, check params!"
-        self.last = dict(grid_points=int(grid_pts.shape[0]), boundary_points=int(tot), kept=int(pts.shape[0]))
+        info = {}
+        if self.con > 0:
+            keep, info = self.component_filter(pts)
+            pts = pts[keep]
+        self.last = dict(grid_points=int(grid_pts.shape[0]), boundary_points=int(tot), kept=int(pts.shape[0]), **info)
         return pts, self.get_point_volumes(pts)
 
 
@@ -172,17 +203,24 @@ def simulator_cloud(points, volumes, density=1e3, lam=1e6, mu=1e6, pin_height=0.
                 pin=(pos[:, 1] < y0 + pin_height).astype(np.int32))
 
 
-if __name__ == "__main__":
+def parser():
     import argparse
-    from . import scene
-    from .nerf.network import NeRFNetwork
     ap = argparse.ArgumentParser(description="sample a simulator point cloud from the (synthetic) checkpoint's density field")
     ap.add_argument("--out", default="model/chair.ply")
     ap.add_argument("--sub_res", type=int, default=60)
     ap.add_argument("--sub_coeff", type=float, default=0.1)
     ap.add_argument("--density_threshold", type=float, default=0.05)
-    a = ap.parse_args()
-    o = scene.default_opt(sub_res=a.sub_res, sub_coeff=a.sub_coeff, density_threshold=a.density_threshold)
+    ap.add_argument("--con", type=int, default=0, help="keep the points of this many largest connected components of the density field; 0 (default) "
+                    "keeps all.  The reference declares --con with default 1 but never applies it, so off is the faithful default")
+    ap.add_argument("--vres", type=int, default=96, help="side of the occupancy lattice that --con labels")
+    return ap
+
+
+if __name__ == "__main__":
+    from . import scene
+    from .nerf.network import NeRFNetwork
+    a = parser().parse_args()
+    o = scene.default_opt(sub_res=a.sub_res, sub_coeff=a.sub_coeff, density_threshold=a.density_threshold, con=a.con, vres=a.vres)
     net = NeRFNetwork(encoding="hashgrid", bound=o["bound"], cuda_ray=True).to("cuda:0").load_checkpoint_dict(scene.make_checkpoint(bound=o["bound"]))
     s = AdaptiveUniformSampling(o, net)
     p, v = s.sample(generator=torch.Generator(device="cuda:0").manual_seed(0))

@@ -254,28 +254,31 @@ class Trainer:
         self.stats["results"].append(result["psnr"])
         return result
 
-    def _geometry(self, resolution, threshold):
+    def _geometry(self, resolution, threshold, components=0):
         from .mesh import density_query
         m = self.model
-        return extract_geometry(m.aabb_infer[:3], m.aabb_infer[3:], resolution=resolution, threshold=threshold, query_func=density_query(m, self.fp16))
+        return extract_geometry(m.aabb_infer[:3], m.aabb_infer[3:], resolution=resolution, threshold=threshold, query_func=density_query(m, self.fp16),
+                                components=components)
 
-    def save_mesh(self, save_path, resolution=256, threshold=10):
+    def save_mesh(self, save_path, resolution=256, threshold=10, components=0):
         """trainer.py:331-354: the `threshold` level set of model.density(pts)['sigma'] (no_grad, autocast(enabled=fp16)) on the resolution^3 lattice
         over aabb_infer, meshed on the device, written as a binary PLY (scene.write_mesh_ply).  `save_path` is required: this Trainer has no workspace
-        or epoch to name a default file after."""
+        or epoch to name a default file after.  components > 0: only that many largest connected components of the above-threshold nodes are meshed
+        (extract_geometry); 0 meshes everything, floaters included."""
         from .scene import write_mesh_ply
         d = os.path.dirname(save_path)
         if d:
             os.makedirs(d, exist_ok=True)
-        vertices, triangles = self._geometry(resolution, threshold)
+        vertices, triangles = self._geometry(resolution, threshold, components)
         write_mesh_ply(save_path, vertices, triangles)
         return vertices, triangles
 
-    def save_point_cloud(self, save_path, resolution=256, threshold=10):
-        """trainer.py:356-378: the vertices of save_mesh's surface as an ASCII PLY (write_to_ply).  `save_path` is required (no workspace / epoch)."""
+    def save_point_cloud(self, save_path, resolution=256, threshold=10, components=0):
+        """trainer.py:356-378: the vertices of save_mesh's surface (`components` as there) as an ASCII PLY (write_to_ply).  `save_path` is required
+        (no workspace / epoch)."""
         d = os.path.dirname(save_path)
         if d:
             os.makedirs(d, exist_ok=True)
-        cloud, _ = self._geometry(resolution, threshold)
+        cloud, _ = self._geometry(resolution, threshold, components)
         write_to_ply(cloud, save_path)
         return cloud
