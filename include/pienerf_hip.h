@@ -569,6 +569,24 @@ int pn_sim_drag_set(void* drag, int n_IP, int vid, int active, double scale, con
 int pn_sim_drag_unproject(const float* depth0, int W, int H, double x, double y, const double* intr4, const double* pose16, const float* ip_pos,
                           int n_IP, void* drag, double* work, void* stream);
 
+/* Arbitrary rest-space points carried by the simulator's GMLS field (csrc/pn_warp_points.hip; simulator/binding.py: PointBinding.warp; INTEGRATION.md
+ * "Deforming mesh").  Per point p, in fp64: pos = sum_{i<8} sum_{c<10} Nx[p,i,c] dof[topo[p,i] 10 + c, :], rounded to fp32 once.  With normals_out:
+ * F[r][j] = sum_i sum_c dNx[p,i,j,c] dof[topo[p,i] 10 + c, r], n' = n0 (f1 x f2) + n1 (f2 x f0) + n2 (f0 x f1) with f_j = column j of F and
+ * n = normals0[p] (cof(F) n: no division, no inverse), normalised in fp64 and rounded to fp32 once; |n'| zero or not finite: normals0[p] unchanged.
+ * Tables, built once at bind time in groups of G = pn_sim_warp_points_group() = 8 points, n_g = ceil(n_pts / G) groups, lane l of a group's wave =
+ * point l / 8, neighbour slot l % 8; rows behind the last point are zeros:
+ *   topo_g [n_g][64] int32      = topo [n_g G, 8] row-major, entries in [0, n_k);
+ *   Nx_g   [n_g][5][64][2] fp64: the lane's 10 weights Nx[p,i,:] as 5 pairs;
+ *   dNx_g  [n_g][15][64][2] fp64: the lane's 30 gradients dNx[p,i,j,c] (flat j 10 + c) as 15 pairs (needed with normals_out only).
+ * Nx_g, dNx_g and dof are read 16 bytes per lane and must be 16-byte aligned.  dof [10 n_k,3] fp64 is read from the pointer at execution time;
+ * normals0 [n_pts,3] fp32; pos_out, normals_out [n_pts,3] fp32 (normals_out NULL: positions only; dNx_g and normals0 may then be NULL).
+ * Each lane sums its slot over c = 0..9 in order, the 8 slots are added as ((s0 + s1) + (s2 + s3)) + ((s4 + s5) + (s6 + s7)): a point's bits depend on
+ * its own row only, not on the other points of the call.  One launch, no atomics, no allocation, no host synchronisation: legal inside a stream
+ * capture.  PN_ERR_ARG for n_pts <= 0, n_k <= 0, a missing or misaligned pointer. */
+int pn_sim_warp_points_group(void);
+int pn_sim_warp_points(int n_pts, int n_k, const int* topo_g, const double* Nx_g, const double* dNx_g, const double* dof, const float* normals0,
+                       float* pos_out, float* normals_out, void* stream);
+
 /* ------------------------------------------------------------------ meshing ---- */
 
 /* Marching cubes (nerf/utils.py:174-205 extract_geometry's mcubes.marching_cubes; csrc/pn_mesh.hip, INTEGRATION.md "Meshing").  `field` is a

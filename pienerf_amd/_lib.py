@@ -119,6 +119,8 @@ SIGNATURES = {
     "pn_sim_drag_force": (i32, [i32, i32, P, P, f64, P, P, P, P, P]),
     "pn_sim_drag_set": (i32, [P, i32, i32, i32, f64, P, P]),
     "pn_sim_drag_unproject": (i32, [P, i32, i32, f64, f64, P, P, P, i32, P, P, P]),
+    "pn_sim_warp_points_group": (i32, []),
+    "pn_sim_warp_points": (i32, [i32, i32, P, P, P, P, P, P, P, P]),
     "pn_mc_work_bytes": (u64, [i32, i32, i32]),
     "pn_mc_count": (i32, [P, i32, i32, i32, f64, P, P, P]),
     "pn_mc_emit": (i32, [P, i32, i32, i32, f64, P, P, P, P]),

@@ -4,8 +4,12 @@ deformed point cloud and the per-frame IP state the reference's ``main_render.py
 
     python -m pienerf_amd.main_render --frames 30 --out output_img/chair [--ply model/chair_0.ply] [--ckpt ws/checkpoints/ngp_ep0300.pth]
            [--W 800 --H 800] [--radius 5 --azimuth 0 --elevation 0 --fovy 50] [--force fx fy fz | --drag X0 Y0 X1 Y1] [--save_ply] [--save_ip_state]
+           [--save_mesh [--mesh_resolution 128] [--mesh_threshold 10] [--mesh_con 0] [--mesh_normals] [--mesh_color]]
 
 Without --ply / --ckpt the synthetic chair of pienerf_amd.scene is used (there are no assets on the GPU box).
+--save_mesh writes the deforming surface: the model's density level set, meshed once at rest, bound to the simulator (Simulator.bind_points) and warped
+by its GMLS field before every frame's substep, as OUT/mesh_{f}.ply with the same triangles in every file — mesh f shows the state img_f.png shows.
+Without --ckpt such a run renders and meshes the SHAPED synthetic checkpoint (its density field has the solid's shape; the plain one's does not).
 Reference: main_gui.py:20-66 (model + simulator construction), nerf/gui.py:556-645 (test_step: IP info -> substep -> render),
 main_render.py:47-104 (frame loop, save_image), simulator/solver.py:109-113 (OutputToPly).
 """
@@ -25,13 +29,31 @@ def build_harness(args):
                             max_iter_num=args.max_iter_num, num_seek_IP=args.num_seek_IP, bound=args.bound, dt_gamma=args.dt_gamma,
                             max_steps=args.max_steps, T_thresh=args.T_thresh, bg_radius=args.bg_radius)
     cloud = scene.cloud_from_ply(args.ply) if args.ply else None
-    h = SimRenderHarness(opt, cloud=cloud, ckpt=None, device=args.device)
+    ckpt = None
+    if args.save_mesh and not args.ckpt:   # a density field with the solid's shape, as python -m pienerf_amd.mesh uses: the plain synthetic field has no surface
+        ckpt = scene.make_checkpoint(bound=args.bound, shaped=True, bg_radius=args.bg_radius)
+    h = SimRenderHarness(opt, cloud=cloud, ckpt=ckpt, device=args.device)
     if args.ckpt:
         path = args.ckpt if os.path.isfile(args.ckpt) else io.latest_checkpoint(args.ckpt)
         if path is None:
             raise FileNotFoundError(f"no checkpoint under {args.ckpt}")
         io.load_checkpoint(h.model, path, model_only=True, allow_pickle=args.trust_ckpt)
     return h
+
+
+def bind_rest_mesh(h, args):
+    """The rest mesh of the harness's model (extract_geometry over aabb_infer) bound to its simulator: (binding, triangles, colors or None)."""
+    from .mesh import density_query, vertex_colors, vertex_normals
+    from .nerf.utils import extract_geometry
+    m = h.model
+    vertices, triangles = extract_geometry(m.aabb_infer[:3], m.aabb_infer[3:], args.mesh_resolution, args.mesh_threshold, density_query(m),
+                                           components=args.mesh_con)
+    if len(vertices) == 0:
+        raise SystemExit(f"--save_mesh: the density field has no level set at --mesh_threshold {args.mesh_threshold}")
+    normals = vertex_normals(vertices, triangles) if (args.mesh_normals or args.mesh_color) else None
+    colors = vertex_colors(m, vertices, normals) if args.mesh_color else None
+    binding = h.sim.bind_points(vertices, normals if args.mesh_normals else None)
+    return binding, triangles, colors
 
 
 def run(args):
@@ -46,6 +68,10 @@ def run(args):
             raise SystemExit("--drag and --force both set the force: choose one")
         h.enable_drag(args.drag_scale)
         h.step(pose=pose, simulate=False)   # the frame the first pick is unprojected against (not written)
+    if args.save_mesh:
+        binding, triangles, colors = bind_rest_mesh(h, args)
+        if not args.quiet:
+            print(f"mesh: {binding.V} vertices, {len(triangles)} triangles; {binding.n_fallback} vertices bound through their nearest integration point")
     written, t0 = [], time.time()
     for f in range(args.frames):
         if args.drag is not None:
@@ -58,6 +84,12 @@ def run(args):
                     print(f"drag: picked IP {vid} at pixel ({x:.1f}, {y:.1f})")
             else:
                 h.move(x, y)
+        if args.save_mesh:   # BEFORE the step: a frame renders the pre-step state (harness.py), so mesh f shows what img_f.png shows
+            h.synchronize()  # the previous frame's substep runs on the harness's side stream
+            w = binding.warp()
+            pos, nrm = w if args.mesh_normals else (w, None)
+            scene.write_mesh_ply(os.path.join(args.out, f"mesh_{f}.ply"), pos.cpu().numpy(), triangles,
+                                 normals=nrm.cpu().numpy() if nrm is not None else None, colors=colors)
         out = h.to_host(h.step(pose=pose, collect_stats=True))
         path = os.path.join(args.out, f"img_{f}.png")
         io.save_image(out["image"], path, args.W, args.H)
@@ -105,6 +137,13 @@ def parser():
     ap.add_argument("--drag_scale", type=float, default=1.0, help="the GUI's force_scale of the drag (mouse wheel, gui.py:857-865)")
     ap.add_argument("--save_ply", action="store_true")
     ap.add_argument("--save_ip_state", action="store_true")
+    ap.add_argument("--save_mesh", action="store_true", help="write the deforming surface mesh of every frame as OUT/mesh_{f}.ply (rest mesh bound to the simulator, "
+                    "warped in one HIP launch per frame); without --ckpt the run uses the shaped synthetic checkpoint")
+    ap.add_argument("--mesh_resolution", type=int, default=128, help="lattice nodes per axis of the rest mesh")
+    ap.add_argument("--mesh_threshold", type=float, default=10.0, help="density level of the surface")
+    ap.add_argument("--mesh_con", type=int, default=0, help="mesh only this many largest connected components (0: everything)")
+    ap.add_argument("--mesh_normals", action="store_true", help="write per-frame vertex normals (rest normals pushed forward by cof(F))")
+    ap.add_argument("--mesh_color", action="store_true", help="write vertex colours, computed once at rest (the model's colour seen along -normal)")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--quiet", action="store_true")
     return ap

@@ -13,6 +13,7 @@ import itertools
 import os
 import time
 
+import numpy as np
 import torch
 
 from ._lib import check, lib, ptr, require_gpu, stream_ptr
@@ -76,6 +77,41 @@ def density_query(model, fp16=False):
         with torch.no_grad(), torch.autocast("cuda", dtype=torch.float16, enabled=bool(fp16)):
             return model.density(pts.to(dev))["sigma"]
     return query
+
+
+def vertex_normals(vertices, triangles):
+    """Area-weighted vertex normals [V,3] fp64 (a torch tensor on the vertices' device; numpy input: on the CPU): per vertex the sum of
+    cross(b - a, c - a) over its incident faces (a, b, c), normalised.  With the project's case table that cross product points out of the
+    above-threshold region, so nothing is flipped.  The sum is ordered (gmls.index_add_ordered): equal meshes give equal bits.  A vertex whose sum is
+    zero or not finite (no face, or faces that cancel) gets (0, 0, 1)."""
+    from .simulator.gmls import index_add_ordered
+    v = vertices if torch.is_tensor(vertices) else torch.from_numpy(np.ascontiguousarray(np.asarray(vertices, np.float64)))
+    v = v.detach().to(torch.float64).reshape(-1, 3)
+    t = triangles if torch.is_tensor(triangles) else torch.from_numpy(np.ascontiguousarray(np.asarray(triangles, np.int64)))
+    t = t.detach().to(device=v.device, dtype=torch.int64).reshape(-1, 3)
+    a, b, c = v[t[:, 0]], v[t[:, 1]], v[t[:, 2]]
+    fn = torch.linalg.cross(b - a, c - a)
+    acc = torch.zeros_like(v)
+    if t.shape[0]:
+        index_add_ordered(acc, t.t().reshape(-1), fn.repeat(3, 1))    # every face once per corner: corner 0 of all faces, then 1, then 2
+    ln = torch.sqrt((acc * acc).sum(-1, keepdim=True))
+    ok = (ln > 0.0) & torch.isfinite(ln)
+    up = torch.tensor([0.0, 0.0, 1.0], dtype=torch.float64, device=v.device)
+    return torch.where(ok, acc / torch.where(ok, ln, torch.ones_like(ln)), up)
+
+
+@torch.no_grad()
+def vertex_colors(model, vertices, normals, chunk=1 << 20):
+    """uint8 RGB [V,3] (numpy): the model's colour at each vertex seen along -normal, i.e. by a viewer looking straight at the surface; the model's
+    own fused forward (NeRFNetwork.forward) in chunks of `chunk` points, the colour clipped to [0, 1], times 255, truncated (io.save_image's rule)."""
+    dev = model.aabb_infer.device
+    x = torch.as_tensor(vertices).detach().to(device=dev, dtype=torch.float32).reshape(-1, 3)
+    d = -torch.as_tensor(normals).detach().to(device=dev, dtype=torch.float32).reshape(-1, 3)
+    out = torch.empty((x.shape[0], 3), dtype=torch.uint8, device=dev)
+    for s in range(0, x.shape[0], chunk):
+        _, rgb = model(x[s:s + chunk], d[s:s + chunk])
+        out[s:s + chunk] = (rgb.to(torch.float32).clamp(0.0, 1.0) * 255.0).to(torch.uint8)
+    return out.cpu().numpy()
 
 
 def parser():

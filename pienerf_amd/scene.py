@@ -95,20 +95,38 @@ def write_ply(path, cloud, binary=True, props=None):
                 f.write((" ".join(repr(float(v)) if isinstance(v, np.floating) else str(int(v)) for v in r) + "\n").encode())
 
 
-def write_mesh_ply(path, vertices, triangles):
+def write_mesh_ply(path, vertices, triangles, normals=None, colors=None):
     """Triangle mesh PLY, binary little endian: vertex `float` x, y, z and face `list uchar int vertex_indices` (Trainer.save_mesh's file; the
     reference writes it with trimesh, which is believed to use this layout: not checked, trimesh is not available to compare against).  read_ply
-    reads its vertex element."""
+    reads its vertex element.  normals [V,3] / colors [V,3] uint8 (this project's options, for the deforming mesh of main_render --save_mesh): the
+    vertex element additionally carries `float` nx, ny, nz / `uchar` red, green, blue, in this order; with neither the bytes are as before."""
     v = np.ascontiguousarray(np.asarray(vertices), dtype="<f4").reshape(-1, 3)
     t = np.asarray(triangles).reshape(-1, 3)
     face = np.zeros(len(t), dtype=[("n", "u1"), ("i", "<i4", (3,))])
     face["n"] = 3
     face["i"] = t
-    hdr = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}", "property float x", "property float y", "property float z",
+    fields, props = [("p", "<f4", (3,))], ["property float x", "property float y", "property float z"]
+    if normals is not None:
+        fields.append(("n", "<f4", (3,)))
+        props += ["property float nx", "property float ny", "property float nz"]
+    if colors is not None:
+        fields.append(("c", "u1", (3,)))
+        props += ["property uchar red", "property uchar green", "property uchar blue"]
+    vert = np.zeros(len(v), dtype=fields)   # packed: 12 (+ 12) (+ 3) bytes per vertex
+    vert["p"] = v
+    for key, a in (("n", normals), ("c", colors)):
+        if a is not None:
+            a = np.asarray(a).reshape(-1, 3)
+            if len(a) != len(v):
+                raise ValueError(f"write_mesh_ply: {len(v)} vertices but {len(a)} rows of {'normals' if key == 'n' else 'colors'}")
+            if key == "c" and a.dtype != np.uint8:
+                raise ValueError("write_mesh_ply: colors must be uint8")
+            vert[key] = a
+    hdr = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}"] + props + [
            f"element face {len(t)}", "property list uchar int vertex_indices", "end_header"]
     with open(path, "wb") as f:
         f.write(("\n".join(hdr) + "\n").encode())
-        f.write(v.tobytes())
+        f.write(vert.tobytes())
         f.write(face.tobytes())
 
 

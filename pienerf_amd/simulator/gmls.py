@@ -50,17 +50,21 @@ def basis_hess(device):
     return h
 
 
-def init_GMLS(r, pos, topo, kernel_pos, chunk=8192):
-    """Shape functions Nx [n,8,10], dNx [n,8,3,10], ddNx [n,8,3,3,10] for points `pos` with neighbour kernels `topo`."""
+def init_GMLS(r, pos, topo, kernel_pos, chunk=8192, hessian=True, gradient=True, singular_ok=False):
+    """Shape functions Nx [n,8,10], dNx [n,8,3,10], ddNx [n,8,3,3,10] for points `pos` with neighbour kernels `topo`.
+    hessian=False leaves ddNx out (None in its place; 5.7 KB per point), gradient=False dNx as well: the same arithmetic for what is returned, the same
+    bits.  singular_ok=True: a point whose moment matrix cannot be inverted (no kernel of `topo` within reach) gets non-finite weights instead of
+    torch.linalg.inv's exception — for callers that check the weights themselves (simulator/binding.py)."""
+    hessian = hessian and gradient
     outs = ([], [], [])
     for s in range(0, pos.shape[0], chunk):
-        res = _init_GMLS_chunk(float(r), pos[s:s + chunk], topo[s:s + chunk], kernel_pos)
+        res = _init_GMLS_chunk(float(r), pos[s:s + chunk], topo[s:s + chunk], kernel_pos, hessian, gradient, singular_ok)
         for o, t in zip(outs, res):
             o.append(t)
-    return tuple(torch.cat(o, dim=0).contiguous() for o in outs)
+    return tuple(torch.cat(o, dim=0).contiguous() if o and o[0] is not None else None for o in outs)
 
 
-def _init_GMLS_chunk(r, pos, topo, kernel_pos):
+def _init_GMLS_chunk(r, pos, topo, kernel_pos, hessian=True, gradient=True, singular_ok=False):
     dev = pos.device
     n = pos.shape[0]
     q = kernel_pos[topo.long()]                       # [n,8,3]
@@ -72,11 +76,13 @@ def _init_GMLS_chunk(r, pos, topo, kernel_pos):
     active = w > 0.0                                   # `if weight <= 0.0: continue` (cpu_utils.py:28-29)
     e = diff / (r * r)
     dw = torch.where(inside[..., None], -6.0 * (om ** 2)[..., None] * e, torch.zeros_like(e))
-    eye = torch.eye(3, dtype=F64, device=dev)
-    ddw = -6.0 * (om ** 2)[..., None, None] * eye / (r * r) + 24.0 * om[..., None, None] * e[..., :, None] * e[..., None, :]
-    ddw = torch.where(inside[..., None, None], ddw, torch.zeros_like(ddw))
     af = active.to(F64)
-    w, dw, ddw = w * af, dw * af[..., None], ddw * af[..., None, None]
+    w, dw = w * af, dw * af[..., None]
+    if hessian:
+        eye = torch.eye(3, dtype=F64, device=dev)
+        ddw = -6.0 * (om ** 2)[..., None, None] * eye / (r * r) + 24.0 * om[..., None, None] * e[..., :, None] * e[..., None, :]
+        ddw = torch.where(inside[..., None, None], ddw, torch.zeros_like(ddw))
+        ddw = ddw * af[..., None, None]
 
     s2 = math.sqrt(2.0)
     const_rows = torch.zeros(6, 10, dtype=F64, device=dev)
@@ -91,22 +97,26 @@ def _init_GMLS_chunk(r, pos, topo, kernel_pos):
         return torch.einsum("ni,nirc,nir->nc", coef, Phi, t)
 
     G = torch.einsum("ni,nirc,nird->ncd", w, Phi, Phi)
-    Gi = torch.linalg.inv(G)
+    Gi = torch.linalg.inv_ex(G).inverse if singular_ok else torch.linalg.inv(G)
     Gp = torch.einsum("ncd,nd->nc", Gi, basis(pos))
+    g0 = torch.einsum("nicb,nb->nic", Probe, Gp)
+    Nx = g0 * w[..., None]
+    if not gradient:
+        return Nx, None, None
     dP = basis_grad(pos)                                # [n,3,10]
     ddP = basis_hess(dev)
     dGp = torch.stack([torch.einsum("ncd,nd->nc", Gi, dP[:, x] - apply(dw[..., x], Gp)) for x in range(3)], dim=1)  # [n,3,10]
+    g1 = torch.einsum("nicb,njb->nijc", Probe, dGp)
+    dNx = g0[:, :, None, :] * dw[..., None] + g1 * w[..., None, None]
+    if not hessian:
+        return Nx, dNx, None
     ddGp = torch.empty(n, 3, 3, 10, dtype=F64, device=dev)
     for x in range(3):
         for y in range(3):
             rhs = ddP[x, y][None, :] - apply(dw[..., x], dGp[:, y]) - apply(dw[..., y], dGp[:, x]) - apply(ddw[..., x, y], Gp)
             ddGp[:, x, y] = torch.einsum("ncd,nd->nc", Gi, rhs)
 
-    g0 = torch.einsum("nicb,nb->nic", Probe, Gp)
-    g1 = torch.einsum("nicb,njb->nijc", Probe, dGp)
     g2 = torch.einsum("nicb,njkb->nijkc", Probe, ddGp)
-    Nx = g0 * w[..., None]
-    dNx = g0[:, :, None, :] * dw[..., None] + g1 * w[..., None, None]
     ddNx = (g0[:, :, None, None, :] * ddw[..., None] + g1[:, :, None, :, :] * dw[:, :, :, None, None] + g1[:, :, :, None, :] * dw[:, :, None, :, None]
             + g2 * w[..., None, None, None])
     return Nx, dNx, ddNx

@@ -528,6 +528,15 @@ class Simulator:
         with self._on_force_stream():
             check(lib().pn_sim_drag_set(ptr(drag), self.n_IP, -1, 0, 0.0, None, stream_ptr()), "sim_drag_set")
 
+    def bind_points(self, points, normals=None):
+        """Binds arbitrary rest-space points [V,3] (the space of IP_pos and of extract_geometry's mesh; taken in fp64) to this simulator: a
+        PointBinding (simulator/binding.py) whose warp() gives their positions — and, with rest `normals` [V,3], their normals — under the current or a
+        snapshot dof in one HIP launch.  Initialisation-time torch; needs only what precompute() builds.  A point takes the 8 kernels of its own
+        kernel-grid cell when all are active, else those of its nearest integration point; ValueError when a point's binding does not reproduce it
+        at the rest state to 1e-9."""
+        from .binding import bind_points
+        return bind_points(self, points, normals)
+
     def update_pos(self):  # solver.py:604-617 (update_pos_kernel) — only used by OutputToPly
         d = self.dof.view(self.n_k, 10, 3)[self.pts_kernel.long()]
         self.pos = torch.einsum("nic,nicr->nr", self.pts_Nx, d)
