@@ -569,6 +569,34 @@ int pn_sim_drag_set(void* drag, int n_IP, int vid, int active, double scale, con
 int pn_sim_drag_unproject(const float* depth0, int W, int H, double x, double y, const double* intr4, const double* pose16, const float* ip_pos,
                           int n_IP, void* drag, double* work, void* stream);
 
+/* Kinematic pins (csrc/pn_pins.hip; Simulator.enable_pin_motion): the pinned points follow a scripted motion.  The system matrix holds
+ * stiff N N^T for every pinned point (build_pin_global), so a prescribed displacement u_p of pin p changes the right-hand side alone, by
+ * stiff sum_p N_p^T u_p; a launch in front of every substep writes rhs_ext = rhs_gravity + that term, and the substep takes rhs_ext in its
+ * rhs_gravity slot.  The motion is evaluated on the device from this state and its own substep clock, so a substep captured into a HIP graph, or
+ * run frames ahead of the render, gets the displacement of ITS time:  substep k uses t = (k + 1) dt, and for a pin with rest position X
+ *     u(t) = offset + T(t) + R(t)(X - c) - (X - c),   T(t) = A sin(2 pi f_T t + phi_T),
+ *     R(t) = the Rodrigues rotation about the unit axis n by the angle theta sin(2 pi f_R t + phi_R)  (theta in radians). */
+typedef struct pn_pin_motion {
+    int64_t k;         /* substeps since the last pn_sim_pins_clock */
+    int active;        /* 0: rhs_ext = rhs_gravity, bit for bit */
+    int reserved;
+    double A[3], f_T, phi_T;
+    double n[3], theta, f_R, phi_R, c[3];
+} pn_pin_motion;
+uint64_t pn_sim_pins_bytes(void);        /* sizeof(pn_pin_motion) = 128 */
+/* Writes `active` (>= 0; -1 keeps it) and the parameters given: translate5_host = (A[3], f_T, phi_T), rotate9_host = (n[3], theta, f_R, phi_R, c[3]);
+ * NULL keeps that part.  Everything finite, |n| = 1 to 1e-9 when theta != 0.  A one-thread launch on `stream`; the clock is left alone. */
+int pn_sim_pins_set(void* state, int n_pin, int active, const double* translate5_host, const double* rotate9_host, void* stream);
+/* k = the clock's new value (>= 0), by a one-thread launch on `stream`. */
+int pn_sim_pins_clock(void* state, int64_t k, void* stream);
+/* rhs_ext [10 n_k,3] = rhs_gravity + stiff sum_p N_p^T u_p((k + 1) dt), then k += 1 (a one-thread launch BEHIND the first: no workgroup reads a
+ * clock that its own launch advances).  Per-kernel CSR over the pins' (pin, neighbour slot) pairs, stably sorted by kernel: pin_bg [n_k + 1] run
+ * starts, pin_of [8 n_pin] the entry's pin, pin_N [8 n_pin,10] its pts_Nx row, in CSR order; pin_X [n_pin,3] rest positions; offsets [n_pin,3] or
+ * NULL.  One workgroup (one wave) per kernel: its lanes stride the run in ascending order and a fixed shuffle tree adds them, so the order of
+ * the sum is a function of the run alone, not of the grid, the launch or the device; no atomics.  Rows of a kernel without an entry, and every row when !active, are copies of rhs_gravity. */
+int pn_sim_pins_rhs(int n_k, int n_pin, void* state, double dt, double stiff, const double* rhs_gravity, const int* pin_bg, const int* pin_of,
+                    const double* pin_N, const double* pin_X, const double* offsets, double* rhs_ext, void* stream);
+
 /* Arbitrary rest-space points carried by the simulator's GMLS field (csrc/pn_warp_points.hip; simulator/binding.py: PointBinding.warp; INTEGRATION.md
  * "Deforming mesh").  Per point p, in fp64: pos = sum_{i<8} sum_{c<10} Nx[p,i,c] dof[topo[p,i] 10 + c, :], rounded to fp32 once.  With normals_out:
  * F[r][j] = sum_i sum_c dNx[p,i,j,c] dof[topo[p,i] 10 + c, r], n' = n0 (f1 x f2) + n1 (f2 x f0) + n2 (f0 x f1) with f_j = column j of F and

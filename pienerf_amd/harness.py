@@ -164,7 +164,7 @@ class SimRenderHarness:
             self._sim_stream = torch.cuda.Stream(self.device)
         self._graph_pose = torch.from_numpy(np.asarray(self.pose, np.float32)).unsqueeze(0).to(self.device)
         self._graph_pose_host = self.pose
-        keep = (self.sim.dof.clone(), self.sim.dof_vel.clone())
+        keep = (self.sim.dof.clone(), self.sim.dof_vel.clone(), self.sim._pin_clock_keep())
         warm = torch.cuda.Stream(self.device)
         warm.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(warm):
@@ -177,10 +177,12 @@ class SimRenderHarness:
             self._graph_out = self._step_body(n_trips, W, H)
         self.sim.dof.copy_(keep[0])       # warm-up advanced the simulator; capture itself executes nothing
         self.sim.dof_vel.copy_(keep[1])
+        self.sim._pin_clock_restore(keep[2])   # ... the pin motion's substep clock: the k-th replayed frame sees the clock of the k-th eager step
         self.sim.reset_warm_start()       # ... and its SVD warm start: a replay from here has the bits of a simulator that never warmed up
         self._graph_trips = n_trips
         self._graph_done = None
         self._graph_drag = self.sim.drag_enabled   # the substep's k_drag_force launch is in the graph or it is not
+        self._graph_pins = self.sim.pin_enabled    # ... and so is its k_pin_rhs launch (Simulator.enable_pin_motion)
         self._graph_form_epoch = self._net_form_epoch()
         return self
 
@@ -196,6 +198,10 @@ class SimRenderHarness:
             raise RuntimeError(f"the network's weights were refreshed into another arithmetic form (pn_net_form) since {what} was captured: its graphs "
                                f"hold the old form's kernels — capture again")
 
+    def _check_pins_captured(self, captured, what, again):
+        if self.sim.pin_enabled and not captured:
+            raise RuntimeError(f"pin motion: {what} was captured before enable_pin_motion(), its substep ignores the pin motion: {again} again")
+
     @torch.no_grad()
     def step_graph(self, pose=None):
         """Replays the captured step.  Outputs are static tensors (overwritten by the next replay); they are complete — including frames
@@ -203,6 +209,7 @@ class SimRenderHarness:
         if getattr(self, "_graph", None) is None:
             self.capture()
         self._check_net_form(self._graph_form_epoch, "the step")
+        self._check_pins_captured(self._graph_pins, "the step graph", "capture()")
         self._check_previous_graph_frame()
         if pose is not None:
             self._graph_pose.copy_(torch.from_numpy(np.asarray(pose, np.float32)).unsqueeze(0))
@@ -298,6 +305,7 @@ class SimRenderHarness:
                                    force_collectives=bool(_force_collectives) and on, sim_on_lanes=sim_on_lanes)
         self.sim.force_hooks = (self._pipe.before_force, self._pipe.after_force) if self._pipe.sim_on_lanes else None
         self._pipe_drag = self.sim.drag_enabled
+        self._pipe_pins = self.sim.pin_enabled
         self._drag_frame = ("pipelined",)
         self._pipe_backend = be
         self._pipe_form_epoch = self._net_form_epoch()
@@ -311,6 +319,7 @@ class SimRenderHarness:
     @torch.no_grad()
     def step_pipelined(self, pose=None):
         self._check_net_form(self._pipe_form_epoch, "the pipeline")
+        self._check_pins_captured(self._pipe_pins, "the pipeline", "capture_pipelined()")
         out = self._pipe.step(pose)
         self.frame = self._pipe.frame
         return out
@@ -624,7 +633,7 @@ class _HipBackend:
         self.pose_pin = [pose0.clone().pin_memory() for _ in range(n_ws)]
         self.pose_key = [pose0.numpy().tobytes()] * n_ws
         self.ip = [tuple(torch.empty((n_IP, c), dtype=torch.float32, device=dev) for c in (3, 9, 27)) for _ in range(n_ws)]
-        keep = (sim.dof.clone(), sim.dof_vel.clone())
+        keep = (sim.dof.clone(), sim.dof_vel.clone(), sim._pin_clock_keep())
         main = torch.cuda.current_stream(dev)
         for ws in range(n_ws):  # warm-up of every workspace outside capture (creates the pn_frame workspaces, the fp16 tables, ...)
             s = self._streams[f"lane{ws // depth}"]
@@ -694,6 +703,7 @@ class _HipBackend:
                     check(lib().pn_copier_wait(self.copier, t.value), "copier_wait")
         sim.dof.copy_(keep[0])      # warm-up advanced the simulator; capture itself executes nothing
         sim.dof_vel.copy_(keep[1])
+        sim._pin_clock_restore(keep[2])   # ... the pin motion's substep clock
         sim.reset_warm_start()      # ... and its SVD warm start: a replay from here has the bits of a simulator that never warmed up
         torch.cuda.synchronize(dev)
 

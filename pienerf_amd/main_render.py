@@ -3,12 +3,15 @@ does for one frame — load a point cloud and a checkpoint, step the simulator, 
 deformed point cloud and the per-frame IP state the reference's ``main_render.py`` reads back from ``./debug``).
 
     python -m pienerf_amd.main_render --frames 30 --out output_img/chair [--ply model/chair_0.ply] [--ckpt ws/checkpoints/ngp_ep0300.pth]
-           [--W 800 --H 800] [--radius 5 --azimuth 0 --elevation 0 --fovy 50] [--force fx fy fz | --drag X0 Y0 X1 Y1] [--save_ply] [--save_ip_state]
+           [--W 800 --H 800] [--radius 5 --azimuth 0 --elevation 0 --fovy 50] [--force fx fy fz | --drag X0 Y0 X1 Y1] [--pin_shake AX AY AZ HZ] [--pin_twist NX NY NZ DEG HZ [--pin_centre X Y Z]] [--save_ply] [--save_ip_state]
            [--save_mesh [--mesh_resolution 128] [--mesh_threshold 10] [--mesh_con 0] [--mesh_normals] [--mesh_color]]
 
 Without --ply / --ckpt the synthetic chair of pienerf_amd.scene is used (there are no assets on the GPU box).
 --save_mesh writes the deforming surface: the model's density level set, meshed once at rest, bound to the simulator (Simulator.bind_points) and warped
 by its GMLS field before every frame's substep, as OUT/mesh_{f}.ply with the same triangles in every file — mesh f shows the state img_f.png shows.
+--pin_shake / --pin_twist move the pinned points of the cloud (Simulator.enable_pin_motion): a sinusoidal translation with amplitude (AX, AY, AZ) at HZ,
+a rotation about the axis (NX, NY, NZ) through --pin_centre (default: the pins' centroid) by DEG sin(2 pi HZ t) degrees; they compose with each other and
+with --force / --drag, and images, --save_ply and --save_mesh follow the moving object.
 Without --ckpt such a run renders and meshes the SHAPED synthetic checkpoint (its density field has the solid's shape; the plain one's does not).
 Reference: main_gui.py:20-66 (model + simulator construction), nerf/gui.py:556-645 (test_step: IP info -> substep -> render),
 main_render.py:47-104 (frame loop, save_image), simulator/solver.py:109-113 (OutputToPly).
@@ -57,6 +60,8 @@ def bind_rest_mesh(h, args):
 
 
 def run(args):
+    if args.pin_centre is not None and args.pin_twist is None:
+        raise SystemExit("--pin_centre is the centre of --pin_twist")
     h = build_harness(args)
     pose = scene.orbit_pose(args.radius, args.azimuth, args.elevation)
     os.makedirs(args.out, exist_ok=True)
@@ -68,6 +73,14 @@ def run(args):
             raise SystemExit("--drag and --force both set the force: choose one")
         h.enable_drag(args.drag_scale)
         h.step(pose=pose, simulate=False)   # the frame the first pick is unprojected against (not written)
+    if args.pin_shake is not None or args.pin_twist is not None:   # kinematic pins: shake the object by its base, twist it by its handle
+        sh, tw = args.pin_shake, args.pin_twist
+        try:
+            h.sim.enable_pin_motion()
+            h.sim.set_pin_motion(translate=(sh[:3], sh[3]) if sh is not None else None,
+                                 rotate=(tw[:3], tw[3], tw[4], 0.0, args.pin_centre) if tw is not None else None)
+        except ValueError as e:   # a cloud without pinned points, a zero axis, a non-finite value
+            raise SystemExit(f"--pin_shake / --pin_twist: {e}")
     if args.save_mesh:
         binding, triangles, colors = bind_rest_mesh(h, args)
         if not args.quiet:
@@ -135,6 +148,11 @@ def parser():
     ap.add_argument("--drag", type=float, nargs=4, default=None, metavar=("X0", "Y0", "X1", "Y1"),
                     help="scripted mouse drag: pick the IP under pixel (X0, Y0) on frame 0, move the cursor linearly to (X1, Y1) over the frames")
     ap.add_argument("--drag_scale", type=float, default=1.0, help="the GUI's force_scale of the drag (mouse wheel, gui.py:857-865)")
+    ap.add_argument("--pin_shake", type=float, nargs=4, default=None, metavar=("AX", "AY", "AZ", "HZ"),
+                    help="move the pinned points by (AX, AY, AZ) sin(2 pi HZ t)")
+    ap.add_argument("--pin_twist", type=float, nargs=5, default=None, metavar=("NX", "NY", "NZ", "DEG", "HZ"),
+                    help="rotate the pinned points about the axis (NX, NY, NZ) by DEG sin(2 pi HZ t) degrees")
+    ap.add_argument("--pin_centre", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"), help="a point on --pin_twist's axis (default: the pins' centroid)")
     ap.add_argument("--save_ply", action="store_true")
     ap.add_argument("--save_ip_state", action="store_true")
     ap.add_argument("--save_mesh", action="store_true", help="write the deforming surface mesh of every frame as OUT/mesh_{f}.ply (rest mesh bound to the simulator, "
