@@ -662,6 +662,34 @@ int pn_train_batch(const float* pose, float fx, float fy, float cx, float cy, in
  * is the row of the batch's view, cells [N] int64 are distinct. */
 int pn_error_map_update(float* map_row, const int64_t* cells, const float* err, int N, void* stream);
 
+/* ------------------------------------------------------------------ image metrics ---- */
+
+/* SSIM of channel-last images (csrc/pn_ssim.hip, pienerf_amd/metrics.py): what torchmetrics' structural_similarity_index_measure
+ * computes for the reference's SSIMMeter (nerf/utils.py:268-302).  pred, truth [B, H, W, C] fp32 contiguous, H, W >= 11, C >= 1, B <= 65535,
+ * H W C < 2^31.  Window: 11 taps g_i = exp(-((i - 5) / 1.5)^2 / 2) / sum (double on the host, rounded to fp32), weight g_i g_j.  Only the
+ * (H - 10) x (W - 10) positions whose whole window lies inside the image exist.  Per position and channel, with w-weighted sums over the window:
+ *     mx = E[x], my = E[y], sxx = E[xx] - mx^2, syy = E[yy] - my^2, sxy = E[xy] - mx my,
+ *     S = ((2 mx my + c1)(2 sxy + c2)) / ((mx^2 + my^2 + c1)(sxx + syy + c2)),   c1 = (0.01 R)^2, c2 = (0.03 R)^2.
+ * out [B] = the mean of S over positions and channels.  The kernels read {c1, c2} from the device buffer c12 [2], so no form of the data range makes
+ * the host wait.  Every entry: no atomics, fixed summation order (equal inputs give equal bits), no allocation, no host synchronisation; PN_ERR_ARG
+ * (nothing launched) for a null pointer or a shape outside the above. */
+/* Bytes of `work` (8-byte aligned) for pn_ssim_range and pn_ssim_forward on [B, H, W, *]: the range kernel's partial extrema and one fp64 partial
+ * per workgroup (16 x 16 output tile) and image.  0 for an illegal shape. */
+uint64_t pn_ssim_work_bytes(int B, int H, int W);
+/* c12 = {(0.01 R)^2, (0.03 R)^2} in fp32.  pred == truth == NULL: R = data_range (> 0, finite), one launch.  Otherwise R = max(pred.max() -
+ * pred.min(), truth.max() - truth.min()) over the n floats of each, two launches (data_range is ignored; two constant images give R = 0 and S = 0/0,
+ * as in the reference; a NaN pixel is skipped by the extrema, where torch's max would return it). */
+int pn_ssim_range(const float* pred, const float* truth, uint64_t n, float data_range, void* work, float* c12, void* stream);
+/* out [B]; with mapA, mapB, mapD (all three or none), each [B, H-10, W-10, C]: B = dS/dsxx, D = dS/dsxy, A = dS/dmx - 2 mx B - my D, the maps
+ * pn_ssim_backward reads.  Two launches (tiles, then the fixed-order sum of their partials). */
+int pn_ssim_forward(const float* pred, const float* truth, int B, int H, int W, int C, const float* c12, void* work, float* out, float* mapA,
+                    float* mapB, float* mapD, void* stream);
+/* grad_pred [B, H, W, C] = grad_out[b] / ((H-10)(W-10)C) * ((w * A)_q + 2 x_q (w * B)_q + y_q (w * D)_q): the gradient of sum_b grad_out[b] out[b]
+ * with respect to pred (R constant; truth gets none).  `*` is the full correlation of a map, zero outside the valid region, with the window, at every
+ * pixel q.  Gather form, one launch. */
+int pn_ssim_backward(const float* pred, const float* truth, int B, int H, int W, int C, const float* mapA, const float* mapB, const float* mapD,
+                     const float* grad_out, float* grad_pred, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -133,6 +133,10 @@ SIGNATURES = {
     "pn_sample_cells": (i32, [P, P, i32, i32, P, P, P]),
     "pn_train_batch": (i32, [P, f32, f32, f32, f32, i32, i32, i32, i32, P, P, P, i32, P, i32, P, P, P, P, P]),
     "pn_error_map_update": (i32, [P, P, P, i32, P]),
+    "pn_ssim_work_bytes": (u64, [i32, i32, i32]),
+    "pn_ssim_range": (i32, [P, P, u64, f32, P, P, P]),
+    "pn_ssim_forward": (i32, [P, P, i32, i32, i32, i32, P, P, P, P, P, P, P]),
+    "pn_ssim_backward": (i32, [P, P, i32, i32, i32, i32, P, P, P, P, P, P]),
 }
 
 _lib = None

@@ -51,6 +51,9 @@ UNITS = {
     # pixel's ray is pn_ray_dir.h's, shared with pn_ray_ops.hip bit for bit
     "pn_train_batch.hip": ["-ffp-contract=off"],
     "pn_components.hip": ["-ffp-contract=off"],  # connected-component labelling: integers only, the flag has nothing to act on
+    # SSIM (metrics.py): every moment is a sum of 11 products in tap order and sigma = E[xx] - mx^2 cancels, so each operation rounds once as written;
+    # tests/ssim_reference.py's fp32 evaluation then has the same error size and sets the tests' tolerance
+    "pn_ssim.hip": ["-ffp-contract=off"],
     "pn_copier.hip": [],  # host code only: frame copies through the HSA runtime (links libhsa-runtime64)
 }
 

@@ -113,6 +113,13 @@ def save_image(image, path, W, H):
     return data
 
 
+def load_image(path):
+    """An image file (what ``save_image`` writes) -> float32 RGB [H, W, 3] in [0, 1]; an alpha channel is dropped."""
+    from PIL import Image
+    with Image.open(path) as img:
+        return torch.from_numpy(np.asarray(img.convert("RGB"), np.float32) / 255)
+
+
 def linear_to_srgb(x):
     """nerf/utils.py:44-46 (applied to the prediction when opt.color_space == 'linear', trainer.py:583-584)."""
     return torch.where(x < 0.0031308, 12.92 * x, 1.055 * x ** 0.41666 - 0.055)

@@ -10,8 +10,9 @@ validation images under ``WS/validation`` and, at the end, the point cloud ``WS/
 the newest checkpoint of the workspace, ``--ckpt scratch`` starts fresh.  ``--test`` loads, evaluates the test split and writes ``WS/meshes``.
 
 Reference: get_opts.py (the shared, training, backbone and data-set groups; defaults and the derived options -O, --dataset_type synthetic,
---patch_size), main_train.py:32-101 (flow).  Not built: --ff, --tcnn, --gui, --clip_text and --rand_pose (refused by name), the LPIPS meter and the
-patch branch's LPIPS term, tensorboard, video writing.
+--patch_size), main_train.py:32-101 (flow).  Validation and test report the PSNR and the SSIM meter (pienerf_amd/metrics.py); ``--ssim_lambda`` puts
+an SSIM term into the patch loss.  Not built: --ff, --tcnn, --gui, --clip_text and --rand_pose (refused by name), the LPIPS meter and the patch
+branch's LPIPS term, tensorboard, video writing.
 """
 import argparse
 import os
@@ -43,7 +44,9 @@ def parser():
     ap.add_argument("--max_ray_batch", type=int, default=4096, help="batch size of rays at inference (without --cuda_ray)")
     ap.add_argument("--patch_size", type=int, default=1,
                     help="train on square patches of this size (1: off; e.g. 64, 32, 16).  The reference adds an LPIPS term on the patches; its weights are "
-                         "not available here, so patches train with the MSE term alone")
+                         "not available here: patches train with the MSE term alone, or with --ssim_lambda with a structural (SSIM) term beside it")
+    ap.add_argument("--ssim_lambda", type=float, default=0.0,
+                    help="weight L in [0, 1] of the patch loss (1 - L) MSE + L (1 - SSIM); needs --patch_size >= 11, the SSIM window.  0: off")
     ap.add_argument("--T_thresh", type=float, default=1e-2, help="stop marching a ray when its transmittance falls below this")
     # network backbone options
     ap.add_argument("--fp16", action="store_true", help="amp mixed precision training")
@@ -86,6 +89,10 @@ def derive(opt):
         opt.error_map = False  # patches ignore the error map
         if opt.num_rays % (opt.patch_size ** 2) != 0:
             raise SystemExit("--patch_size: its square must divide --num_rays")
+    if not 0.0 <= opt.ssim_lambda <= 1.0:
+        raise SystemExit("--ssim_lambda: a weight in [0, 1]")
+    if opt.ssim_lambda > 0 and opt.patch_size < 11:
+        raise SystemExit("--ssim_lambda > 0 needs --patch_size >= 11: SSIM's 11 x 11 window has to fit into a patch")
     for flag, what in (("ff", "--ff (fully-fused MLP backbone)"), ("tcnn", "--tcnn (TCNN backbone)"), ("gui", "--gui (training inside the GUI)")):
         if getattr(opt, flag):
             raise SystemExit(f"{what} is not part of this project: the nerf.network backbone trains headless")
@@ -124,7 +131,7 @@ def build(opt):
 
 def run(opt):
     """main_train.py:50-101.  Returns what happened: the trainer, the epoch / global_step it started from, the per-step losses, the last validation
-    and the test result ({'loss', 'psnr'} or None) and the files written."""
+    and the test result ({'loss', 'psnr', 'ssim'} or None) and the files written."""
     if not opt.path:
         raise SystemExit("--path: the data set directory (transforms*.json)")
     say = (lambda *a: None) if opt.quiet else print
@@ -146,7 +153,8 @@ def run(opt):
     if res["losses"]:
         say(f"loss {np.mean(res['losses'][:5]):.5f} -> {np.mean(res['losses'][-20:]):.5f} over {len(res['losses'])} steps")
     if trainer.stats["valid_loss"]:
-        res["valid"] = {"loss": trainer.stats["valid_loss"][-1], "psnr": trainer.stats["results"][-1]}
+        res["valid"] = {"loss": trainer.stats["valid_loss"][-1], "psnr": trainer.stats["results"][-1],
+                        "ssim": trainer.valid_result["ssim"] if trainer.valid_result else None}   # None: no validation in this run (resumed stats)
         say(f"validation: {res['valid']}")
     test_loader = NeRFDataset(opt, device=opt.device, type="test").dataloader()
     if test_loader.has_gt:   # blender sets have test images, COLMAP's interpolated test poses do not

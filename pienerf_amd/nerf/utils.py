@@ -1,6 +1,7 @@
 """``get_rays`` (inference and training forms), ``get_pnts_in_grids`` and the meshing functions ``extract_fields``, ``extract_geometry`` and ``write_to_ply`` with the reference's
 signatures (nerf/utils.py:54-138, 355-386, 174-205, 341-351), backed by HIP kernels: the density lattice is evaluated and meshed on the device
-(pienerf_amd.mesh, marching cubes in csrc/pn_mesh.hip).  The rest of the reference's nerf/utils.py (metrics, seeding) is off-path."""
+(pienerf_amd.mesh, marching cubes in csrc/pn_mesh.hip).  The reference's PSNR and SSIM meters (:231-302) are in pienerf_amd/metrics.py; the rest
+(the LPIPS meter, seeding) is off-path."""
 import numpy as np
 import torch
 

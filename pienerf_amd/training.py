@@ -16,7 +16,7 @@ import os
 import numpy as np
 import torch
 
-from . import io
+from . import io, metrics
 from .nerf.utils import error_map_update, extract_geometry, get_rays, write_to_ply
 
 
@@ -94,8 +94,8 @@ class _LoaderFeed:
 class Trainer:
     def __init__(self, model, opt, lr=1e-2, iters=30000, update_extra_interval=16, num_rays=4096, ema_decay=None, fp16=False, name="ngp",
                  eval_interval=50, max_keep_ckpt=2):
-        """opt: the render options of a step (dt_gamma, max_steps, T_thresh, ...) and, for ``fit`` / ``evaluate_loader``, ``color_space`` and
-        ``patch_size``.  name, eval_interval, max_keep_ckpt: trainer.py:17-31, used by ``fit``.
+        """opt: the render options of a step (dt_gamma, max_steps, T_thresh, ...) and, for ``fit`` / ``evaluate_loader``, ``color_space``,
+        ``patch_size`` and ``ssim_lambda`` (``train_step``).  name, eval_interval, max_keep_ckpt: trainer.py:17-31, used by ``fit``.
         ema_decay: main_train.py:78 passes 0.95; None (default) trains without an average, like Trainer's own default (trainer.py:19).
         fp16 (trainer.py:20,84: ``--fp16``): the steps run under autocast with a GradScaler — half hash tables, half nn.Linear, and the half
         scatter-add of the grid's backward (gridencoder.cu:324-331)."""
@@ -111,13 +111,15 @@ class Trainer:
         self.name, self.eval_interval, self.max_keep_ckpt = name, int(eval_interval), int(max_keep_ckpt)
         self.epoch, self.workspace, self.error_map = 0, None, None   # error_map: the data set's, set by fit (trainer.py:391)
         self.stats = {"loss": [], "valid_loss": [], "results": [], "checkpoints": [], "best_result": None}   # trainer.py:92-98
+        self.valid_result = None   # what fit's last validation returned (evaluate_loader)
 
     def _render_opts(self):
         keep = ("dt_gamma", "max_steps", "T_thresh", "num_steps", "upsample_steps")   # the last two: the sampler of a model without cuda_ray (get_opts.py:19-22)
         return {k: self.opt[k] for k in keep if k in self.opt}
 
     def train_step(self, data):
-        """trainer.py:158-207 (the image-supervised branch)."""
+        """trainer.py:158-207 (the image-supervised branch).  opt['ssim_lambda'] = L > 0 with opt['patch_size'] >= 11: the loss is
+        (1 - L) MSE + L (1 - ssim(patches, data_range=1)), the structural term standing where the reference's patch branch has its LPIPS term (:218)."""
         images = data["images"]
         C = images.shape[-1]
         if C == 4 and not self.model.bg_radius > 0:  # random per-pixel background under the alpha matte (trainer.py:186-196); not with a background model
@@ -128,13 +130,18 @@ class Trainer:
             bg, gt_rgb = 1, images[..., :3] * images[..., 3:] + (1 - images[..., 3:])
         else:
             bg, gt_rgb = 1, images
-        all_rays = int(self.opt.get("patch_size", 1)) != 1   # patches are rendered whole (trainer.py:201); their LPIPS term (:218) is not built
+        patch = int(self.opt.get("patch_size", 1))
+        all_rays = patch != 1   # patches are rendered whole (trainer.py:201); their LPIPS term (:218) is not built
         outputs = self.model.render(data["rays_o"], data["rays_d"], staged=False, bg_color=bg, perturb=True, force_all_rays=all_rays, **self._render_opts())
         pred_rgb = outputs["image"]
         loss = self.criterion(pred_rgb, gt_rgb).mean(-1)   # per ray [1, N]
         if self.error_map is not None and "inds_coarse" in data:   # trainer.py:224-246: the sampled cells' moving average of the per-ray loss
             error_map_update(self.error_map[int(data["index"][0])], data["inds_coarse"], loss)
         loss = loss.mean()
+        lam = float(self.opt.get("ssim_lambda", 0) or 0)
+        if lam > 0 and patch >= metrics.WINDOW:
+            # get_rays' patch batches are patch-major, then patch row, then patch column: [1, N, 3] is [N / p^2, p, p, 3]
+            loss = (1 - lam) * loss + lam * (1 - metrics.ssim(pred_rgb.reshape(-1, patch, patch, 3), gt_rgb.reshape(-1, patch, patch, 3), data_range=1.0))
         return pred_rgb, gt_rgb, loss
 
     def train(self, dataset, steps):
@@ -219,20 +226,23 @@ class Trainer:
             losses += epoch_losses
             self.save_checkpoint()
             if self.epoch % self.eval_interval == 0 and valid_loader is not None:
-                self.evaluate_loader(valid_loader)
+                self.valid_result = self.evaluate_loader(valid_loader)
         return losses
 
     @torch.no_grad()
     def evaluate_loader(self, loader, name=None):
         """evaluate_one_epoch (trainer.py:689-792) with the PSNR meter: every view of ``loader`` rendered in eval() mode on the averaged weights against
         its ground truth over white; the predictions go to ``{workspace}/validation/{name}_{i:04d}.png`` (through linear_to_srgb when the colour space
-        is linear).  Returns {'loss': mean MSE, 'psnr': mean PSNR} and records them in stats['valid_loss'] / stats['results']."""
+        is linear).  Returns {'loss': mean MSE, 'psnr': mean PSNR, 'ssim': mean SSIM} and records the first two in stats['valid_loss'] /
+        stats['results'].  'ssim' is the SSIMMeter's (metrics.ssim with data_range=None per view, summed on the device and read once at the end);
+        None when a view is smaller than the 11 x 11 window."""
         name = name if name is not None else f"{self.name}_ep{self.epoch:04d}"
         self.model.eval()
         if self.ema is not None:
             self.ema.store()
             self.ema.copy_to()
         total_loss, total_psnr, n = 0.0, 0.0, 0
+        ssim_meter = metrics.SSIMMeter(device=next(self.model.parameters()).device)
         for data in loader:
             n += 1
             images = data["images"]   # [1, H, W, C]
@@ -244,12 +254,16 @@ class Trainer:
             mse = float(torch.mean((pred - gt) ** 2))
             total_loss += mse
             total_psnr += -10 * float(np.log10(mse))   # PSNRMeter (nerf/utils.py:249-256)
+            if ssim_meter is not None and min(H, W) >= metrics.WINDOW:
+                ssim_meter.update(pred, gt)
+            else:
+                ssim_meter = None
             if self.workspace is not None:
                 shown = io.linear_to_srgb(pred) if self.opt.get("color_space", "srgb") == "linear" else pred
                 io.save_image(shown[0], os.path.join(self.workspace, "validation", f"{name}_{n:04d}.png"), W, H)
         if self.ema is not None:
             self.ema.restore()
-        result = {"loss": total_loss / max(n, 1), "psnr": total_psnr / max(n, 1)}
+        result = {"loss": total_loss / max(n, 1), "psnr": total_psnr / max(n, 1), "ssim": ssim_meter.measure() if ssim_meter is not None and n else None}
         self.stats["valid_loss"].append(result["loss"])
         self.stats["results"].append(result["psnr"])
         return result
