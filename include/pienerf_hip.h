@@ -499,7 +499,7 @@ int pn_sim_stepforward(int n_k, int n_IP, int iters, double dt, double dx, const
  * csr_pos (may be NULL; needs dNx_csr): inverse of csr_buf, csr_pos[csr_buf[e]] = e; calc_elastic then also writes P once per
  * neighbour slot in CSR order and the gather has no index left to follow. */
 uint64_t pn_sim_work_doubles(int n_k, int n_IP);
-/* Simulator.stepforward in its CELL form (csrc/pn_sim.hip: k_cells_elastic_gather): calc_elastic (cuda_utils.py:83-121) and collect_rhs_IP (:124-151)
+/* Simulator.stepforward in its CELL form (csrc/pn_sim_cells.h: k_cells_elastic_gather): calc_elastic (cuda_utils.py:83-121) and collect_rhs_IP (:124-151)
  * of a local/global iteration as ONE launch, the dense product (solver.py:600-601) as the other — 1 + 2 iters launches per substep instead of 1 + 3 iters.
  * All integration points of one kernel-grid cell share their 8 neighbour kernels (solver.py:186-205); the caller sorts the points by cell and cuts the
  * cells into chunks of <= pn_sim_cells_chunk_ips() points:
@@ -522,7 +522,7 @@ int pn_sim_stepforward_cells(int n_k, int n_chunks, int iters, double dt, double
                              const double* lam_cell, const int* kp_bg, const int* kp_pos, const double* Ainv, const double* Mmat, const double* dof_rest,
                              const double* rhs_rest, const double* rhs_gravity, const double* dof_f, double* dof, double* dof_vel, double* work,
                              int mcadams_sweeps, void* stream);
-/* The local/global iterations of a substep as ONE persistent kernel of n_wg workgroups (one per CU; csrc/pn_sim.hip: k_substep_coop) instead of four
+/* The local/global iterations of a substep as ONE persistent kernel of n_wg workgroups (one per CU; csrc/pn_sim_coop.h: k_substep_coop) instead of four
  * launches per iteration: same arguments and results as pn_sim_stepforward (tolerance of the summation orders, ~1e-13 relative), `work` prepared by
  * pn_sim_prepare, `coop` >= pn_sim_coop_bytes(n_k, n_IP, n_wg) bytes prepared by pn_sim_coop_prepare, which also returns plan[3] = {pieces, entries
  * per slot, pieces per kernel at most} to pass on.  pn_sim_coop_bytes returns 0 and pn_sim_coop_prepare PN_ERR_ARG when the scene does not fit the persistent form (n_k > 204,
@@ -531,8 +531,6 @@ int pn_sim_stepforward_cells(int n_k, int n_chunks, int iters, double dt, double
 uint64_t pn_sim_coop_bytes(int n_k, int n_IP, int n_wg);
 int pn_sim_coop_prepare(int n_k, int n_IP, int n_wg, const int* csr_bg, const int* csr_cnt, void* coop, int* plan_out, void* stream);
 int pn_sim_coop_status(const void* coop, int* timed_out);
-/* Timing experiments only (environment PN_SIM_COOP_DBG & 4): per-phase tick sums of workgroup 0, see csrc/pn_sim.hip. */
-int pn_sim_coop_clocks(const void* coop, uint64_t* ticks9);
 int pn_sim_stepforward_coop(int n_k, int n_IP, int iters, double dt, double dx, const int* topo, const double* mu, const double* lam, const double* dNx,
                             const double* dNx_csr, const int* csr_pos, const double* Ainv, const double* Mmat, const double* dof_rest,
                             const double* rhs_rest, const double* rhs_gravity, const double* dof_f, double* dof, double* dof_vel, double* work,

@@ -35,7 +35,7 @@ extern thread_local char pn_err_buf[512];
     } while (0)
 
 static inline uint32_t pn_div_up(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
-// Value read from the environment (test hooks and the persistent simulator's settings: INTEGRATION.md, "Environment knobs").
+// Value read from the environment (test hooks: INTEGRATION.md, "Environment knobs").
 static inline uint32_t pn_env_u32(const char* name, uint32_t dflt) {
     const char* v = getenv(name);
     if (!v || !*v) return dflt;

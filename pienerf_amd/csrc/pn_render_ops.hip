@@ -22,6 +22,37 @@
 
 thread_local char pn_err_buf[512] = {0};
 
+// ------------------------------------------------------------------------------------------------ library-wide entries (beside the buffer they report)
+extern "C" int pn_device_cu_count(void) {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return -1;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return -1;
+    return n;
+}
+
+extern "C" int pn_stream_create_cu_mask(uint32_t total_cu, uint32_t first_cu, uint32_t n_cu, int invert, void** stream_out) {
+    PN_REQUIRE(stream_out && total_cu > 0 && total_cu <= 1024 && n_cu > 0 && first_cu + n_cu <= total_cu);
+    uint32_t mask[32];
+    const uint32_t words = (total_cu + 31) / 32;
+    for (uint32_t w = 0; w < words; w++) mask[w] = 0;
+    for (uint32_t i = 0; i < total_cu; i++) {
+        const bool in = i >= first_cu && i < first_cu + n_cu;
+        if (in != (invert != 0)) mask[i / 32] |= 1u << (i % 32);
+    }
+    hipStream_t s = nullptr;
+    PN_HIP_CHECK(hipExtStreamCreateWithCUMask(&s, words, mask));
+    *stream_out = (void*)s;
+    return PN_OK;
+}
+
+extern "C" int pn_stream_destroy(void* stream) {
+    PN_REQUIRE(stream);
+    PN_HIP_CHECK(hipStreamDestroy((hipStream_t)stream));
+    return PN_OK;
+}
+
+extern "C" const char* pn_version(void) { return "pienerf_hip 0.1.0 gfx950"; }
+extern "C" const char* pn_last_error(void) { return pn_err_buf; }
 extern "C" int pn_pnts_in_grids(int n_vtx, int n_grid, const float* pnts, const float* bbmin, float hgs, const int* resolution, int* pig_cnt,
                                 int* pig_bgn, int* pig_idx, int* err_flag, void* stream) {
     PN_REQUIRE(n_vtx > 0 && n_grid > 0 && pnts && bbmin && resolution && pig_cnt && pig_bgn && pig_idx);

@@ -293,7 +293,7 @@ class SimRenderHarness:
         if (world > 1 and (dedicated_sim_default(world) if dedicated_sim is None else bool(dedicated_sim)) and rank == sim_owner
                 and dist.get_backend(group) == "nccl" and os.environ.get("PN_SIM_COOP", "") == "1"):
             # this GPU only simulates: with PN_SIM_COOP=1 the substep's local/global iterations run as one persistent kernel on (almost) every CU
-            # (csrc/pn_sim.hip: k_substep_coop; 0.24 instead of 0.28 ms).  Opt-in: it has never run beside RCCL's kernels (one-GPU test box), and a
+            # (csrc/pn_sim_coop.h: k_substep_coop; 0.24 instead of 0.28 ms).  Opt-in: it has never run beside RCCL's kernels (one-GPU test box), and a
             # persistent kernel that cannot get all its CUs ends with a flag and an invalid state instead of a slower step.  Never beside renders:
             # its workgroups and those of the fused composite/compaction would wait for each other.  (A gloo group is the one-GPU dry run.)
             self.sim.enable_persistent()
@@ -381,7 +381,7 @@ class SimRenderHarness:
         return {"ok": ok, "frame": int(pipe.last_frame), "max_abs_diff": worst}
 
     def _check_persistent_substep(self):
-        """A persistent substep whose workgroups could not all become resident ends with a flag instead of hanging (csrc/pn_sim.hip); its DOFs
+        """A persistent substep whose workgroups could not all become resident ends with a flag instead of hanging (csrc/pn_sim_coop.h); its DOFs
         are garbage.  Checked where the host synchronises anyway."""
         if self.sim.persistent and self.sim.persistent_timed_out():
             raise RuntimeError("the persistent substep (pn_sim_stepforward_coop) timed out at a device-wide barrier: the simulator state is invalid "

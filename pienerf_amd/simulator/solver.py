@@ -31,7 +31,7 @@ class _null_ctx:
         return False
 
 
-CELL_CHUNK_IPS = 32   # points per chunk of the substep's cell form = pn_sim_cells_chunk_ips() (csrc/pn_sim.hip: PN_CELL_IPS), checked in _prepare_cells
+CELL_CHUNK_IPS = 32   # points per chunk of the substep's cell form = pn_sim_cells_chunk_ips() (csrc/pn_sim_cells.h: PN_CELL_IPS), checked in _prepare_cells
 
 
 DRAG_SCALE_MIN, DRAG_SCALE_MAX = 1e-3, 5e1   # gui.py:865
@@ -96,7 +96,7 @@ class Simulator:
         self.device = torch.device(device)
         # svd: which decomposition stands in for wp.svd3 (cuda_utils.py:107) in calc_elastic.  "jacobi" (default): the converged, warm-started threshold
         # Jacobi; "mcadams" / "mcadams:N": the published algorithm wp.svd3 implements (McAdams et al., TR1690) with N fixed sweeps (default 8, the setting
-        # of double-precision builds; 4 is the paper's single-precision setting) — csrc/pn_sim.hip: svd3_mcadams.  None: environment PN_SIM_SVD.
+        # of double-precision builds; 4 is the paper's single-precision setting) — csrc/pn_sim_svd.h: svd3_mcadams.  None: environment PN_SIM_SVD.
         svd = (svd if svd is not None else os.environ.get("PN_SIM_SVD", "jacobi")).strip().lower()
         name, _, n = svd.partition(":")
         if name not in ("jacobi", "mcadams") or (n and not n.isdigit()) or (name == "jacobi" and n):

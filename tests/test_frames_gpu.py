@@ -208,7 +208,7 @@ def _rccl_worker(rank, world, port, out_dir, persistent):
     m._net_sig = None
     assert torch.equal(before, m.encoder.embeddings.data)
     if persistent:
-        assert h.sim.enable_persistent()   # the substep's iterations as ONE cooperative kernel (csrc/pn_sim.hip: k_substep_coop) beside RCCL's kernels
+        assert h.sim.enable_persistent()   # the substep's iterations as ONE cooperative kernel (csrc/pn_sim_coop.h: k_substep_coop) beside RCCL's kernels
     h.capture_frame_parallel(lanes=2, n_trips=8, _force_collectives=True)   # graphs on 2 lanes + simulator stream + RCCL broadcasts on the comm stream + copier thread
     p = h._pipe
     assert p.world == 1 and p.collectives and h._pipe_backend.copier is not None

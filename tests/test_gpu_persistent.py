@@ -1,4 +1,4 @@
-"""The substep's local/global iterations as ONE persistent kernel (pn_sim_stepforward_coop, csrc/pn_sim.hip: k_substep_coop) against the launch form
+"""The substep's local/global iterations as ONE persistent kernel (pn_sim_stepforward_coop, csrc/pn_sim_coop.h: k_substep_coop) against the launch form
 (pn_sim_stepforward) and the fp64 CPU oracle: same trajectory, bit-reproducible, inside captured graphs, and the fallback when a scene does not fit."""
 import numpy as np
 import pytest

@@ -45,6 +45,17 @@ def test_svd_choice_is_an_argument_not_a_library_global():
         assert h.pn_sim_calc_elastic(1, dummy, dummy, dummy, dummy, dummy, None, sweeps, None) == 1   # PN_ERR_ARG
 
 
+def test_persistent_phase_clocks_are_the_timing_builds_alone():
+    """The persistent substep's phase clocks belong to the timing build (-DPN_SIM_STAMPS=1, tools/build_variant.py): the default library neither
+    exports nor declares their read-back entry, and the bindings have no signature for it (tools/time_sim.py looks it up on the library it runs on)."""
+    import ctypes
+    from pienerf_amd import _lib
+    so = ctypes.CDLL(_lib.LIB_PATH)
+    name = "pn_sim_coop_clocks"
+    assert not hasattr(so, name)
+    assert name not in _declared_symbols() and name not in _lib.SIGNATURES
+
+
 def test_simulator_lifecycle_before_initialize():
     """reset_warm_start() before initialize() does nothing; enable_persistent() refuses svd='mcadams' (the persistent form has the default
     decomposition only) and leaves the form as it was."""
@@ -333,7 +344,7 @@ def test_environment_reads_are_the_documented_allowlist():
     allow = {
         "PN_CC_GRID", "PN_CC_TRIP0",                          # test hooks of the fused composite + compaction (tests/test_gpu_edges.py)
         "PN_NET_FORM",                                        # network form (tests/test_gpu_netform.py)
-        "PN_SIM_SVD", "PN_SIM_FORM", "PN_SIM_COOP", "PN_SIM_COOP_RESERVE", "PN_SIM_COOP_EU", "PN_SIM_COOP_DBG",
+        "PN_SIM_SVD", "PN_SIM_FORM", "PN_SIM_COOP", "PN_SIM_COOP_RESERVE",
         "PN_LIB_PATH",                                        # another build of the library (tools/build_variant.py)
     }
     pkg = os.path.join(ROOT, "pienerf_amd")

@@ -2,7 +2,7 @@
 // write their doubles with relaxed agent-scope stores (sc1: written through to the memory side, no L2 write-back of anything else), wait for the
 // stores' acknowledgement (s_waitcnt vmcnt(0)), publish a per-workgroup generation tag, the consumers poll all tags with ONE coalesced load per
 // round and then read the data with relaxed agent-scope loads (sc1: never served from this XCD's possibly stale L2 line).  This is the primitive
-// of the persistent substep (pn_sim.hip: k_substep_persistent); tools/calib_barrier.hip measured the counting barriers and the fenced form.
+// of the persistent substep (pn_sim_coop.h: k_substep_coop); tools/calib_barrier.hip measured the counting barriers and the fenced form.
 //   hipcc --offload-arch=gfx950 -O3 -o bin/calib_exchange calib_exchange.hip && bin/calib_exchange
 #include <hip/hip_runtime.h>
 #include <cstdio>

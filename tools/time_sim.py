@@ -1,6 +1,8 @@
 #!/usr/bin/env python
 """stepforward(sim_iters) of the chair simulator alone on the GPU: ms per substep from a captured graph (what the frame pipeline replays).
-    python tools/time_sim.py [--iters 10] [--reps 300] [--drag]        (PN_SIM_FORM=csr: the CSR launch form instead of the cell form)"""
+    python tools/time_sim.py [--iters 10] [--reps 300] [--drag]        (PN_SIM_FORM=csr: the CSR launch form instead of the cell form)
+With --persistent on the timing build (PN_VARIANT_UNITS=pn_sim.hip python tools/build_variant.py simstamps -DPN_SIM_STAMPS=1, then
+PN_LIB_PATH=pienerf_amd/lib/variants/simstamps.so): also the persistent kernel's phase clocks."""
 import argparse
 import os
 import sys
@@ -9,6 +11,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pienerf_amd import scene  # noqa: E402
+from pienerf_amd._lib import lib, ptr  # noqa: E402
 from pienerf_amd.simulator.solver import Simulator  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -43,11 +46,11 @@ with torch.cuda.stream(s):
 s.synchronize()
 ms = e0.elapsed_time(e1) / args.reps
 disp = float((sim.dof - sim.dof_rest).abs().max())
-if args.persistent and sim._coop is not None and int(os.environ.get("PN_SIM_COOP_DBG", "0")) & 4:
+# the timing build (-DPN_SIM_STAMPS=1, see tools/sim_stamps.py) exports the persistent kernel's phase clocks; no other build has the symbol
+if args.persistent and sim._coop is not None and hasattr(lib(), "pn_sim_coop_clocks"):
     import ctypes as C
-    from pienerf_amd._lib import lib, ptr
     ticks = (C.c_uint64 * 9)()
-    lib().pn_sim_coop_clocks(ptr(sim._coop[0]), ticks)
+    assert lib().pn_sim_coop_clocks(ptr(sim._coop[0]), ticks) == 0
     launches = 20 + 1 + 20 + args.reps  # eager steps, capture warm-up... every launch since prepare
     names = ["integration points", "exchange 1", "pieces", "exchange 2", "assembly", "rows", "exchange 3", "assembly: loads, until the rank passes", "kernel start (fill)"]
     tot = sum(ticks)
