@@ -34,9 +34,11 @@ UNITS = {
     "pn_ray_ops.hip": ["-ffp-contract=off"],
     "pn_train_ops.hip": ["-ffp-contract=off"],
     "pn_grid_state.hip": ["-ffp-contract=off"],
-    "pn_nerf_forward.hip": ["-ffp-contract=fast"],
-    "pn_encoder_grad.hip": ["-ffp-contract=fast"],
-    "pn_grid_nd.hip": ["-ffp-contract=fast"],
+    "pn_nerf_forward.hip": ["-ffp-contract=fast"],   # level table, SH forward, the fused network
+    "pn_encoder_grad.hip": ["-ffp-contract=fast"],   # SH dy_dx and backward
+    # the stand-alone hash-grid op, D = 2..5: forward, dy_dx, backward, total variation.  Contracts like nvcc does, so forward and dy_dx equal the
+    # reference kernel's contracting build bit for bit
+    "pn_grid_op.hip": ["-ffp-contract=fast"],
     "pn_background.hip": ["-ffp-contract=off"],  # shares pn_sph.h with pn_ray_ops.hip (the coordinate bit for bit) and blends with two roundings; the network tile contracts inside itself
     # NeRFRenderer.run fused + the masked colour query: the ray-side arithmetic (z, positions, deltas, alpha, the cdf's interpolation, the blend's two
     # roundings) rounds once per operation like the torch op sequence it restates (run_ops); tolerance work, so this is a choice of the closer restatement,

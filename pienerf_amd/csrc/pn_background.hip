@@ -96,7 +96,7 @@ __device__ __forceinline__ void bg_encode_level(float scale, uint32_t offset, ui
 #pragma unroll
         for (int idx = 0; idx < 4; idx++) {
             const float w = (1 * w0[idx & 1]) * w1[idx >> 1];
-            r0 = fmaf(w, e[idx].x, r0);   // results[ch] += w * grid[index + ch], contracted as nvcc contracts it (pn_grid_nd.hip does the same)
+            r0 = fmaf(w, e[idx].x, r0);   // results[ch] += w * grid[index + ch], contracted as nvcc contracts it (pn_grid_op.hip does the same)
             r1 = fmaf(w, e[idx].y, r1);
         }
         out2[0] = r0;

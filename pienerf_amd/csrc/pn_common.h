@@ -83,7 +83,7 @@ struct PnGridLevels {
     uint32_t hashmap_size[PN_MAX_LEVELS];  // offsets[l+1] - offsets[l]
     uint32_t resolution[PN_MAX_LEVELS];    // ceil(scale) + 1
     float scale[PN_MAX_LEVELS];            // exp2f(l*S)*H - 1
-    uint32_t dense[PN_MAX_LEVELS];         // 0: hashed (fast_hash), else number of dims entering the direct index (3 = fully dense)
+    uint32_t dense[PN_MAX_LEVELS];         // 0: hashed (fast_hash), else number of dims entering the direct index (D = fully dense)
     uint32_t mask[PN_MAX_LEVELS];          // hashmap_size - 1 when it is a power of two, else 0
     uint32_t nomod[PN_MAX_LEVELS];         // 1 when the direct index is provably < hashmap_size (no modulo needed)
 };
@@ -97,7 +97,7 @@ struct PnFusedLevel { float scale; uint32_t offset, m1, m2, mask, dense, dm, xm;
 struct PnByteLevel { float scale; uint32_t off_b, p1b, p2b, m1d, m2d, mb, xmb; };
 static_assert(sizeof(PnByteLevel) == sizeof(PnFusedLevel), "both level records share the kernels' LDS slot");
 
-int pn_fill_grid_levels(PnGridLevels* g, const int* offsets_host, uint32_t L, uint32_t C, float S, uint32_t H, uint32_t gridtype,
+int pn_fill_grid_levels(PnGridLevels* g, const int* offsets_host, uint32_t L, uint32_t C, uint32_t D, float S, uint32_t H, uint32_t gridtype,
                         int align_corners);
 
 // The packed network context (pn_net in the C ABI).

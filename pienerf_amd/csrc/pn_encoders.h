@@ -1,22 +1,23 @@
-// Index / constant helpers shared by the encoder kernels (pn_nerf_forward.hip: forward + fused network; pn_encoder_grad.hip: dy_dx,
-// backward, total variation).  gfx950 only.
+// Helpers shared by the encoder kernels (pn_grid_op.hip: the stand-alone hash-grid op; pn_nerf_forward.hip: SH forward + fused network;
+// pn_encoder_grad.hip: SH dy_dx and backward).  gfx950 only.
 #pragma once
 #include "pn_common.h"
 
-// get_grid_index for D = 3 (gridencoder.cu:65-84); `dense` = 0 -> fast_hash, else number of strided dims.
-struct LevelIdx { uint32_t dense, hs, mask, nomod, stride1; };
-__device__ __forceinline__ LevelIdx level_idx(const PnGridLevels& lv, uint32_t level, int align_corners) {
-    return LevelIdx{lv.dense[level], lv.hashmap_size[level], lv.mask[level], lv.nomod[level],
-                    align_corners ? lv.resolution[level] : lv.resolution[level] + 1};
+// Half(w * float(v)) as c10::Half computes it: the float product is rounded to float FIRST and then to half (two roundings).  Written
+// naively, `(_Float16)(w * (float)v)` is fused by hipcc into v_fma_mixlo_f16, which rounds the exact product ONCE, straight to half — a
+// different result whenever the float rounding lands on a half tie (tests/test_gpu_half.py caught it: isolated features one half ulp off the oracle).
+// The empty asm keeps the float product a value of its own.
+__device__ __forceinline__ _Float16 half_of_product(float w, _Float16 v) {
+    float p = w * (float)v;
+    asm volatile("" : "+v"(p));
+    return (_Float16)p;
 }
-__device__ __forceinline__ uint32_t grid_index3(const LevelIdx& L, uint32_t g0, uint32_t g1, uint32_t g2) {
-    if (L.dense == 0) {
-        const uint32_t index = g0 ^ (g1 * 2654435761u) ^ (g2 * 805459861u);
-        return L.mask ? (index & L.mask) : (index % L.hs);
-    }
-    const uint32_t index = g0 + (L.dense > 1 ? g1 * L.stride1 : 0u) + (L.dense > 2 ? g2 * L.stride1 * L.stride1 : 0u);
-    return L.nomod ? index : (index % L.hs);
-}
+template <typename T>
+__device__ __forceinline__ T rounded_product(float w, T v);
+template <>
+__device__ __forceinline__ float rounded_product<float>(float w, float v) { return w * v; }
+template <>
+__device__ __forceinline__ _Float16 rounded_product<_Float16>(float w, _Float16 v) { return half_of_product(w, v); }
 
 
 // Real SH basis in the reference's sign convention (shencoder.cu:50-68); constants are the closed forms of its comments.
@@ -33,16 +34,5 @@ __device__ __forceinline__ uint32_t grid_index3(const LevelIdx& L, uint32_t g0, 
 #define SH_C3E 1.4453057213202769f   /* sqrt(105)/(4 sqrt(pi)) */
 
 
-// training-side launchers (pn_encoder_grad.hip) the forward entry points chain into when dy_dx is requested
-int pn_grid_dy_dx_launch(const float* inputs, const float* embeddings, const PnGridLevels& lv, uint32_t B, uint32_t C, int align_corners, uint32_t interp,
-                         float* dy_dx, hipStream_t st);
+// training-side launcher (pn_encoder_grad.hip) the SH forward entry point chains into when dy_dx is requested
 int pn_sh_dy_dx_launch(const float* inputs, float* dy_dx, uint32_t B, uint32_t C, hipStream_t st);
-// input dimensions 2, 4, 5 of the stand-alone grid op (pn_grid_nd.hip; gridencoder.cu:386-399,430-444): fp32, forward (+ dy_dx) and backward
-int pn_grid_nd_forward_launch(const float* inputs, const float* embeddings, const int* offsets_host, float* outputs, uint32_t B, uint32_t D, uint32_t C,
-                              uint32_t L, float S, uint32_t H, float* dy_dx, uint32_t gridtype, int align_corners, uint32_t interp, int out_bl_major,
-                              hipStream_t st);
-int pn_grid_nd_grad_tv_launch(const float* inputs, const float* embeddings, float* grad, const int* offsets_host, float weight, uint32_t B, uint32_t D, uint32_t C,
-                              uint32_t L, float S, uint32_t H, uint32_t gridtype, int align_corners, hipStream_t st);
-int pn_grid_nd_backward_launch(const float* grad, const float* inputs, const int* offsets_host, float* grad_embeddings, uint32_t B, uint32_t D, uint32_t C,
-                               uint32_t L, float S, uint32_t H, const float* dy_dx, float* grad_inputs, uint32_t gridtype, int align_corners, uint32_t interp,
-                               hipStream_t st);

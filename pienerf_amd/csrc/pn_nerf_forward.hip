@@ -22,7 +22,7 @@
 #include "pn_sh_bands.h"
 
 // ------------------------------------------------------------------------------------------------ level table
-int pn_fill_grid_levels(PnGridLevels* g, const int* offsets_host, uint32_t L, uint32_t C, float S, uint32_t H, uint32_t gridtype,
+int pn_fill_grid_levels(PnGridLevels* g, const int* offsets_host, uint32_t L, uint32_t C, uint32_t D, float S, uint32_t H, uint32_t gridtype,
                         int align_corners) {
     if (L == 0 || L > PN_MAX_LEVELS) return PN_ERR_ARG;
     g->L = L;
@@ -31,171 +31,24 @@ int pn_fill_grid_levels(PnGridLevels* g, const int* offsets_host, uint32_t L, ui
         const float scale = exp2f(l * S) * H - 1.0f;            // gridencoder.cu:133
         const uint32_t res = (uint32_t)ceilf(scale) + 1;        // :134
         const uint32_t hs = (uint32_t)(offsets_host[l + 1] - offsets_host[l]);
+        if (hs == 0) return PN_ERR_ARG;
         // replay get_grid_index's stride loop (gridencoder.cu:65-84) to learn whether this level is hashed
         uint32_t stride = 1, dims = 0;
-        for (uint32_t d = 0; d < 3 && stride <= hs; d++) { stride *= align_corners ? res : (res + 1); dims++; }
+        for (uint32_t d = 0; d < D && stride <= hs; d++) { stride *= align_corners ? res : (res + 1); dims++; }
         const bool hashed = (gridtype == 0 && stride > hs);
         g->offset[l] = (uint32_t)offsets_host[l];
         g->hashmap_size[l] = hs;
         g->resolution[l] = res;
         g->scale[l] = scale;
-        g->dense[l] = hashed ? 0u : dims;  // number of dims that enter the direct index (3 = fully dense)
+        g->dense[l] = hashed ? 0u : dims;  // number of dims that enter the direct index (D = fully dense)
         g->mask[l] = (hs & (hs - 1)) == 0 ? hs - 1 : 0u;
-        // fully dense, untiled: max index = (res+1)^3 - 1 < stride <= hs, so `% hs` is the identity
-        g->nomod[l] = (!hashed && dims == 3 && !align_corners && gridtype == 0) ? 1u : 0u;
+        // fully dense, untiled: max index = (res+1)^D - 1 < stride <= hs, so `% hs` is the identity
+        g->nomod[l] = (!hashed && dims == D && !align_corners && gridtype == 0) ? 1u : 0u;
     }
     return PN_OK;
 }
 
-// ------------------------------------------------------------------------------------------------ op-level grid encoder
-
-// One thread per (sample, level); blockIdx.y = level keeps one level's table hot in the XCD L2s (gridencoder.cu:103,388).
-// T = float: kernel_grid<float,3,C>.  T = _Float16: kernel_grid<at::Half,3,C> — the table and the outputs are half, positions and weights
-// stay float, and `results[ch] += w * grid[index + ch]` rounds the float product to half and adds half + half (c10::Half operators).
-template <uint32_t C, typename T>
-__device__ __forceinline__ void grid_encode_one(float in0, float in1, float in2, const T* __restrict__ emb, const PnGridLevels& lv, uint32_t level, int align_corners,
-                                                uint32_t interp, T (&res)[C]) {
-#pragma unroll
-    for (uint32_t c = 0; c < C; c++) res[c] = (T)0.0f;
-    if (in0 < 0 || in0 > 1 || in1 < 0 || in1 > 1 || in2 < 0 || in2 > 1) return;  // gridencoder.cu:113-133
-    const T* __restrict__ table = emb + (size_t)lv.offset[level] * C;
-    const LevelIdx LI = level_idx(lv, level, align_corners);
-    const float scale = lv.scale[level];
-    float pos[3] = {in0, in1, in2};
-    uint32_t pg[3];
-#pragma unroll
-    for (int d = 0; d < 3; d++) {
-        pos[d] = fmaf(pos[d], scale, align_corners ? 0.0f : 0.5f);  // explicit single rounding, as in the oracle
-        pg[d] = (uint32_t)floorf(pos[d]);
-        pos[d] -= (float)pg[d];
-        if (interp == 1) pos[d] = pos[d] * pos[d] * (3.0f - 2.0f * pos[d]);
-    }
-#pragma unroll
-    for (uint32_t idx = 0; idx < 8; idx++) {
-        float w = 1;
-        uint32_t pl[3];
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-            if ((idx & (1u << d)) == 0) { w *= 1 - pos[d]; pl[d] = pg[d]; }
-            else { w *= pos[d]; pl[d] = pg[d] + 1; }
-        }
-        const uint32_t index = grid_index3(LI, pl[0], pl[1], pl[2]) * C;
-        if (sizeof(T) == 4 && C == 2) {
-            const float2 v = *reinterpret_cast<const float2*>(table + index);
-            res[0] += (T)(w * v.x);
-            res[1] += (T)(w * v.y);
-        } else {
-#pragma unroll
-            for (uint32_t c = 0; c < C; c++) res[c] = res[c] + rounded_product<T>(w, table[index + c]);
-        }
-    }
-}
-
-// [L,B,C] output (the reference kernel's own layout, gridencoder.cu:105): blockIdx.y = level, a thread per sample — the launch sweeps one level's
-// table at a time (it stays in the XCD L2s), neighbouring lanes write neighbouring rows.
-template <uint32_t C, typename T>
-__global__ void __launch_bounds__(256) k_grid_encode(const float* __restrict__ inputs, const T* __restrict__ emb, PnGridLevels lv, uint32_t B,
-                                                     int align_corners, uint32_t interp, T* __restrict__ outputs) {
-    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    const uint32_t level = blockIdx.y;
-    T res[C];
-    grid_encode_one<C, T>(inputs[b * 3], inputs[b * 3 + 1], inputs[b * 3 + 2], emb, lv, level, align_corners, interp, res);
-    T* out = outputs + ((size_t)level * B + b) * C;
-#pragma unroll
-    for (uint32_t c = 0; c < C; c++) out[c] = res[c];
-}
-
-// [B,L*C] output (what gridencoder/grid.py:57 obtains with an extra permute pass).  A thread per sample that wrote its C values of every level
-// straight to its row put neighbouring lanes' stores L*C*4 bytes apart (0.309 ms per 1.02 M samples against 0.172 for [L,B,C]); a thread per
-// (sample, level) with the level varying fastest writes coalesced but gathers from all L tables at once (0.306 ms: the tables no longer take turns
-// in L2).  Here a workgroup keeps its 256 samples, walks the levels like the [L,B,C] launch does — the workgroups of a launch move through the
-// levels roughly together — collects the rows in LDS (row stride padded by one bank) and writes them out whole.
-template <uint32_t C, typename T>
-__global__ void __launch_bounds__(256) k_grid_encode_rows(const float* __restrict__ inputs, const T* __restrict__ emb, PnGridLevels lv, uint32_t B,
-                                                          int align_corners, uint32_t interp, T* __restrict__ outputs) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char rows_raw[];
-    T* rows = reinterpret_cast<T*>(rows_raw);
-    const uint32_t row = lv.L * C, stride = row + (sizeof(T) == 4 ? 1 : 2);
-    const uint32_t b0 = blockIdx.x * 256u, b = b0 + threadIdx.x;
-    float in0 = -1.f, in1 = -1.f, in2 = -1.f;  // past the end: encoded as out of range, never written
-    if (b < B) { in0 = inputs[b * 3]; in1 = inputs[b * 3 + 1]; in2 = inputs[b * 3 + 2]; }
-    for (uint32_t level = 0; level < lv.L; level++) {
-        T res[C];
-        grid_encode_one<C, T>(in0, in1, in2, emb, lv, level, align_corners, interp, res);
-#pragma unroll
-        for (uint32_t c = 0; c < C; c++) rows[threadIdx.x * stride + level * C + c] = res[c];
-    }
-    __syncthreads();
-    const uint32_t n_rows = min(256u, B - b0);
-    for (uint32_t i = threadIdx.x; i < n_rows * row; i += 256) outputs[(size_t)b0 * row + i] = rows[(i / row) * stride + (i % row)];
-}
-
-template <typename T>
-static int grid_encode_launch(const float* inputs, const T* embeddings, const int* offsets_host, T* outputs, uint32_t B, uint32_t D, uint32_t C,
-                              uint32_t L, float S, uint32_t H, uint32_t gridtype, int align_corners, uint32_t interp, int out_bl_major,
-                              PnGridLevels* lv_out, hipStream_t st) {
-    PN_REQUIRE(inputs && embeddings && offsets_host && outputs);
-    PN_REQUIRE(D == 3);                                   // D = 2, 4, 5 (gridencoder.cu:386-395): fp32 in pn_grid_nd.hip; the half table form is D = 3 only
-    PN_REQUIRE(C == 1 || C == 2 || C == 4 || C == 8);     // gridencoder.cu:376-382
-    PN_REQUIRE(gridtype <= 1 && interp <= 1);
-    PnGridLevels lv;
-    if (pn_fill_grid_levels(&lv, offsets_host, L, C, S, H, gridtype, align_corners)) { PN_REQUIRE(L >= 1 && L <= PN_MAX_LEVELS); }
-    if (out_bl_major) {
-        const size_t lds = (size_t)256 * (L * C + (sizeof(T) == 4 ? 1 : 2)) * sizeof(T);
-        PN_REQUIRE(lds <= 150 * 1024);
-        const dim3 grid(pn_div_up(B, 256), 1, 1);
-#define PN_ROWS_LAUNCH(C_)                                                                                                                        \
-    do {                                                                                                                                          \
-        if (lds > 64 * 1024) /* opted into per call: rows this long (C = 8 with 16 levels) are not on any hot path */                             \
-            PN_HIP_CHECK(hipFuncSetAttribute((const void*)k_grid_encode_rows<C_, T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));     \
-        k_grid_encode_rows<C_, T><<<grid, 256, lds, st>>>(inputs, embeddings, lv, B, align_corners, interp, outputs);                            \
-    } while (0)
-        switch (C) {
-            case 1: PN_ROWS_LAUNCH(1); break;
-            case 2: PN_ROWS_LAUNCH(2); break;
-            case 4: PN_ROWS_LAUNCH(4); break;
-            default: PN_ROWS_LAUNCH(8); break;
-        }
-#undef PN_ROWS_LAUNCH
-    } else {
-        const dim3 grid(pn_div_up(B, 256), L, 1);
-        switch (C) {
-            case 1: k_grid_encode<1, T><<<grid, 256, 0, st>>>(inputs, embeddings, lv, B, align_corners, interp, outputs); break;
-            case 2: k_grid_encode<2, T><<<grid, 256, 0, st>>>(inputs, embeddings, lv, B, align_corners, interp, outputs); break;
-            case 4: k_grid_encode<4, T><<<grid, 256, 0, st>>>(inputs, embeddings, lv, B, align_corners, interp, outputs); break;
-            default: k_grid_encode<8, T><<<grid, 256, 0, st>>>(inputs, embeddings, lv, B, align_corners, interp, outputs); break;
-        }
-    }
-    PN_LAUNCH_CHECK();
-    if (lv_out) *lv_out = lv;
-    return PN_OK;
-}
-
-extern "C" int pn_grid_encode_forward(const float* inputs, const float* embeddings, const int* offsets_host, float* outputs, uint32_t B, uint32_t D,
-                                      uint32_t C, uint32_t L, float S, uint32_t H, float* dy_dx, uint32_t gridtype, int align_corners,
-                                      uint32_t interp, int out_bl_major, void* stream) {
-    if (B == 0) return PN_OK;  // empty tensors have null data pointers
-    if (D != 3)                // gridencoder.cu:393-398: D = 2, 4, 5 (anything else: "GridEncoding: D must be 2, 3, 4, 5" -> PN_ERR_ARG)
-        return pn_grid_nd_forward_launch(inputs, embeddings, offsets_host, outputs, B, D, C, L, S, H, dy_dx, gridtype, align_corners, interp, out_bl_major,
-                                         (hipStream_t)stream);
-    PnGridLevels lv;
-    const int rc = grid_encode_launch<float>(inputs, embeddings, offsets_host, outputs, B, D, C, L, S, H, gridtype, align_corners, interp, out_bl_major,
-                                             &lv, (hipStream_t)stream);
-    if (rc) return rc;
-    if (dy_dx) return pn_grid_dy_dx_launch(inputs, embeddings, lv, B, C, align_corners, interp, dy_dx, (hipStream_t)stream);  // training side (pn_encoder_grad.hip)
-    return PN_OK;
-}
-
-extern "C" int pn_grid_encode_forward_half(const float* inputs, const uint16_t* embeddings, const int* offsets_host, uint16_t* outputs, uint32_t B,
-                                           uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H, uint32_t gridtype, int align_corners,
-                                           uint32_t interp, int out_bl_major, void* stream) {
-    if (B == 0) return PN_OK;
-    return grid_encode_launch<_Float16>(inputs, reinterpret_cast<const _Float16*>(embeddings), offsets_host, reinterpret_cast<_Float16*>(outputs), B, D,
-                                        C, L, S, H, gridtype, align_corners, interp, out_bl_major, nullptr, (hipStream_t)stream);
-}
-
-
+// ------------------------------------------------------------------------------------------------ SH encoder op
 __global__ void __launch_bounds__(256) k_sh_encode(const float* __restrict__ inputs, float* __restrict__ outputs, uint32_t B, uint32_t C) {
     const uint32_t b = threadIdx.x + blockIdx.x * blockDim.x;
     if (b >= B) return;
@@ -435,7 +288,7 @@ extern "C" int pn_net_create(pn_net** out, const float* embeddings, const int* o
     PN_REQUIRE(L == 16 && C == 2);  // the architecture of nerf/network.py:14-95 / nerf/encoding.py:40-70
     pn_net* n = new pn_net();
     memset(n, 0, sizeof(*n));
-    if (pn_fill_grid_levels(&n->levels, offsets_host, L, C, per_level_scale_log2, base_resolution, 0, 0)) { delete n; return PN_ERR_ARG; }
+    if (pn_fill_grid_levels(&n->levels, offsets_host, L, C, 3, per_level_scale_log2, base_resolution, 0, 0)) { delete n; return PN_ERR_ARG; }
     PnFusedLevel fl[16];
     PnByteLevel bl[16];
     for (uint32_t l = 0; l < L; l++) {

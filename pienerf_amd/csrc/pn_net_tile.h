@@ -18,22 +18,6 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// Half(w * float(v)) as c10::Half computes it: the float product is rounded to float FIRST and then to half (two roundings).  Written
-// naively, `(_Float16)(w * (float)v)` is fused by hipcc into v_fma_mixlo_f16, which rounds the exact product ONCE, straight to half — a
-// different result whenever the float rounding lands on a half tie (tests/test_gpu_half.py caught it: isolated features one half ulp off the oracle).
-// The empty asm keeps the float product a value of its own.
-__device__ __forceinline__ _Float16 half_of_product(float w, _Float16 v) {
-    float p = w * (float)v;
-    asm volatile("" : "+v"(p));
-    return (_Float16)p;
-}
-template <typename T>
-__device__ __forceinline__ T rounded_product(float w, T v);
-template <>
-__device__ __forceinline__ float rounded_product<float>(float w, float v) { return w * v; }
-template <>
-__device__ __forceinline__ _Float16 rounded_product<_Float16>(float w, _Float16 v) { return half_of_product(w, v); }
-
 // ------------------------------------------------------------------------------------------------ SH (degree <= 4)
 // ------------------------------------------------------------------------------------------------ SH (degree <= 4)
 __device__ __forceinline__ void sh16(float x, float y, float z, float* o) {

@@ -306,7 +306,7 @@ def test_grid_encode_half_equals_the_reference_half_kernel(mods, ckpt):
                                                        (5, 8, 1, False, 1)])
 def test_grid_encode_other_input_dims_equal_the_reference_kernel(mods, D, C, gridtype, align, interp):
     """kernel_grid<float, D, C> for D = 2, 4, 5 (gridencoder.cu:386-399), kernel_grid_backward + kernel_input_backward (:430-444): the stand-alone op's
-    other input dimensions (csrc/pn_grid_nd.hip) against the reference's own kernels, and the CPU oracle (oracle/grid_nd_oracle.cpp) against them too.
+    other input dimensions (csrc/pn_grid_op.hip) against the reference's own kernels, and the CPU oracle (oracle/grid_nd_oracle.cpp) against them too.
     Forward + dy_dx: <= 2e-6 against the contracting build (same arithmetic, one rounding of `pos`); backward: fp32 atomics in any order, 1e-4."""
     from pienerf_amd.gridencoder.grid import level_table_offsets
     ref, fma, ours = mods

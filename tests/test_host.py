@@ -45,6 +45,22 @@ def test_svd_choice_is_an_argument_not_a_library_global():
         assert h.pn_sim_calc_elastic(1, dummy, dummy, dummy, dummy, dummy, None, sweeps, None) == 1   # PN_ERR_ARG
 
 
+def test_grid_op_refuses_shapes_it_is_not_built_for():
+    """The stand-alone hash-grid op is built for D = 2..5 and C = 1, 2, 4, 8 in fp32, and its half-table form for D = 3 alone (gridencoder.grid routes
+    the other dimensions to the fp32 kernels under autocast): anything else is refused before anything is enqueued."""
+    import ctypes
+    from pienerf_amd import _lib
+    h, dummy = _lib.lib(), ctypes.c_void_p(16)
+    off = np.array([0, 64, 128], np.int32)
+    B, L, S, H = 8, 2, 1.0, 4
+    for D in (2, 4, 5):
+        assert h.pn_grid_encode_forward_half(dummy, dummy, off.ctypes.data, dummy, B, D, 2, L, S, H, 0, 0, 0, 1, None) == 1   # PN_ERR_ARG
+        assert h.pn_grid_encode_backward_half(dummy, dummy, off.ctypes.data, dummy, B, D, 2, L, S, H, 0, 0, 0, None) == 1
+    assert h.pn_grid_encode_backward_half(dummy, dummy, off.ctypes.data, dummy, B, 3, 1, L, S, H, 0, 0, 0, None) == 1   # channel pairs: C even
+    for D, C in ((1, 2), (6, 2), (3, 3)):
+        assert h.pn_grid_encode_forward(dummy, dummy, off.ctypes.data, dummy, B, D, C, L, S, H, None, 0, 0, 0, 1, None) == 1
+
+
 def test_persistent_phase_clocks_are_the_timing_builds_alone():
     """The persistent substep's phase clocks belong to the timing build (-DPN_SIM_STAMPS=1, tools/build_variant.py): the default library neither
     exports nor declares their read-back entry, and the bindings have no signature for it (tools/time_sim.py looks it up on the library it runs on)."""
