@@ -595,6 +595,56 @@ int pn_sim_pins_clock(void* state, int64_t k, void* stream);
 int pn_sim_pins_rhs(int n_k, int n_pin, void* state, double dt, double stiff, const double* rhs_gravity, const int* pin_bg, const int* pin_of,
                     const double* pin_N, const double* pin_X, const double* offsets, double* rhs_ext, void* stream);
 
+/* Contact with planes and spheres (csrc/pn_contact.hip; Simulator.enable_contact): an explicit penalty on the right-hand side.  A
+ * launch in front of every substep writes rhs_out = rhs_in + the contact term of the state that substep starts from, and the substep takes rhs_out in
+ * its rhs_gravity slot; the matrix, Ainv and the substep's kernels stay as they are.  All fp64.  For integration point i with m_i = rho[i] dx^3,
+ *     x_i = sum_{slot<8} sum_{c<10} Nx[i,slot,c] dof[topo[i,slot] 10 + c, :],  v_i the same over dof_vel   (pn_ip_row_acc's order, not rounded to fp32)
+ * the colliders 0 .. n-1 are visited in index order, each giving a signed distance d and a unit normal nh out of the solid:
+ *     plane (p, nh): d = nh.(x - p);  sphere (p, R): d = |x - p| - R, nh = (x - p)/|x - p|;  container (p, R): d = R - |x - p|, nh = -(x - p)/|x - p|
+ *     (|x - p| = 0: nh = (0, 1, 0) before the container's sign), and with w = v_i - v (the collider's velocity), w_n = w.nh, w_t = w - w_n nh:
+ *     delta = max(h - d, 0)                       delta = 0: this collider adds exactly nothing
+ *     a_n = (kappa delta + beta min(max(-w_n, 0) dt, delta)) / dt^2,   a_t = min(mu a_n, |w_t| / dt)
+ *     a_i += a_n nh - a_t w_t / |w_t|             (second term only when |w_t| > 0)
+ *     rhs_out[k 30 + j 3 + r] = rhs_in[...] + sum_e m_i Nx[i,slot,j] a_i[r]  over the (i, slot) entries e of kernel k's run, ascending.
+ * The system matrix is at least M / dt^2, so a point's response to its own term is at most dt^2 a_n <= (kappa + beta) delta.  Layout of the state: */
+#define PN_CONTACT_SLOTS 8
+enum { PN_CONTACT_EMPTY = 0, PN_CONTACT_PLANE = 1, PN_CONTACT_SPHERE = 2, PN_CONTACT_CONTAINER = 3 };
+typedef struct pn_contact_collider {
+    int type;          /* PN_CONTACT_*; 0: the slot is empty */
+    int reserved;
+    double p[3];       /* a point of the plane / the sphere's centre */
+    double n[3];       /* the plane's unit normal, out of the solid */
+    double R;          /* the sphere's radius */
+    double v[3];       /* the collider's velocity */
+} pn_contact_collider;
+typedef struct pn_contact_state {
+    int active;        /* 0: rhs_out = rhs_in, bit for bit */
+    int n;             /* 1 + the highest slot in use (<= 8); 0: rhs_out = rhs_in, bit for bit */
+    double kappa;      /* stiffness, in (0, 1] */
+    double beta;       /* damping, in [0, 1] */
+    double mu;         /* friction, >= 0 */
+    double h;          /* thickness, >= 0: contact begins at d < h */
+    pn_contact_collider c[PN_CONTACT_SLOTS];
+} pn_contact_state;
+uint64_t pn_sim_contact_bytes(void);     /* sizeof(pn_contact_state) = 744 */
+/* Writes `active` (>= 0; -1 keeps it) and, with params4_host = (kappa, beta, mu, h) != NULL, the parameters: finite, kappa in (0, 1], beta in [0, 1],
+ * mu >= 0, h >= 0, else PN_ERR_ARG.  A one-thread launch on `stream`. */
+int pn_sim_contact_set_params(void* state, int active, const double* params4_host, void* stream);
+/* Writes slot `index` (0 .. 7) and recomputes n.  geom10_host = (p[3], n[3], R, v[3]), finite; a plane's normal is a unit vector to 1e-9, a sphere's
+ * or container's R > 0, else PN_ERR_ARG; type PN_CONTACT_EMPTY clears the slot (geom10_host may be NULL).  A one-thread launch on `stream`. */
+int pn_sim_contact_set_collider(void* state, int index, int type, const double* geom10_host, void* stream);
+/* rhs_out [10 n_k,3] = rhs_in + the contact term; rhs_in is left untouched and rhs_out is another buffer.  topo [n_IP,8], rho [n_IP], Nx [n_IP,8,10];
+ * kernel_bg / kernel_cnt [n_k] and buffer [8 n_IP] (entry = point 8 + slot) the per-kernel CSR of pn_sim_stepforward, Nx_csr [8 n_IP,10] the Nx rows in
+ * that order.  With accel_out [n_IP,3]: TWO launches, the measured faster form — a thread per point writes accel_out = a_i (zeros for a
+ * point not in contact), then a workgroup of four waves per kernel, thread t taking the run's entries t, t + 256, ... in ascending order, adds
+ * m_i Nx a_i: shuffle tree per wave, then the waves in order through LDS.  accel_out NULL: ONE launch, the same workgroups with every entry evaluating
+ * its point itself (8 x redundant across a point's kernels; every workgroup runs the same code on the same inputs, so all agree on a point to the
+ * bit) — the same bits in rhs_out.  No atomics: the order of every sum is a function of the kernel's run alone.  A kernel none of whose points
+ * is in contact, and every kernel when !active or n == 0, copies rhs_in bit for bit.  No allocation, no host synchronisation, capturable. */
+int pn_sim_contact_rhs(int n_k, int n_IP, const void* state, double dt, double dx, const double* dof, const double* dof_vel, const int* topo,
+                       const double* rho, const double* Nx, const int* kernel_bg, const int* kernel_cnt, const int* buffer, const double* Nx_csr,
+                       const double* rhs_in, double* rhs_out, double* accel_out, void* stream);
+
 /* Arbitrary rest-space points carried by the simulator's GMLS field (csrc/pn_warp_points.hip; simulator/binding.py: PointBinding.warp; INTEGRATION.md
  * "Deforming mesh").  Per point p, in fp64: pos = sum_{i<8} sum_{c<10} Nx[p,i,c] dof[topo[p,i] 10 + c, :], rounded to fp32 once.  With normals_out:
  * F[r][j] = sum_i sum_c dNx[p,i,j,c] dof[topo[p,i] 10 + c, r], n' = n0 (f1 x f2) + n1 (f2 x f0) + n2 (f0 x f1) with f_j = column j of F and

@@ -122,6 +122,10 @@ SIGNATURES = {
     "pn_sim_pins_set": (i32, [P, i32, i32, P, P, P]),
     "pn_sim_pins_clock": (i32, [P, C.c_int64, P]),
     "pn_sim_pins_rhs": (i32, [i32, i32, P, f64, f64, P, P, P, P, P, P, P, P]),
+    "pn_sim_contact_bytes": (u64, []),
+    "pn_sim_contact_set_params": (i32, [P, i32, P, P]),
+    "pn_sim_contact_set_collider": (i32, [P, i32, i32, P, P]),
+    "pn_sim_contact_rhs": (i32, [i32, i32, P, f64, f64, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "pn_sim_warp_points_group": (i32, []),
     "pn_sim_warp_points": (i32, [i32, i32, P, P, P, P, P, P, P, P]),
     "pn_mc_work_bytes": (u64, [i32, i32, i32]),

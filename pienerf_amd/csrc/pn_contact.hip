@@ -1,0 +1,261 @@
+// Contact with planes and spheres (include/pienerf_hip.h: pn_contact_state).
+//
+// Ainv is pre-inverted, so contact is an explicit penalty on the right-hand side, scaled by m / dt^2 so that a point's own response to it is at most
+// (kappa + beta) times its penetration.  The force depends on the integration points' current positions and velocities, so — the drag's argument
+// (pn_drag.hip) — it is evaluated on the device: k_contact_points and k_contact_rhs, enqueued in front of every substep, write rhs_out = rhs_in + the
+// contact term from a small state in device memory (parameters, 8 collider slots) and the dof / dof_vel that substep starts from.  A substep captured into a HIP graph,
+// or run frames ahead of the render in the pipelined harness, gets the contact force of ITS OWN state, and a collider moved by the host between two
+// replays is followed without a recapture.
+#include <math.h>
+
+#include "pn_common.h"
+#include "pn_sim_ip.h"
+
+static_assert(sizeof(pn_contact_collider) == 88, "pn_contact_collider: 88 bytes (pienerf_amd/simulator/solver.py: CONTACT_COLLIDER_DTYPE)");
+static_assert(sizeof(pn_contact_state) == 744, "pn_contact_state: 744 bytes (pienerf_amd/simulator/solver.py allocates it as 93 doubles)");
+static_assert(PN_CONTACT_SLOTS == 8, "pn_contact_state: 8 collider slots");
+
+#define PN_CONTACT_THREADS 256   // four waves per GMLS kernel; fixed: the order of the sum must not depend on the device
+#define PN_CONTACT_WAVES (PN_CONTACT_THREADS / 64)
+
+// ------------------------------------------------------------------------------------------------ the law, per integration point
+// a += a_n n - a_t w_t / |w_t| over the colliders 0 .. n-1 in index order; returns whether any collider is penetrated (delta > 0).  A collider with
+// delta = 0 adds exactly nothing.
+__device__ __forceinline__ bool pn_contact_law(const pn_contact_state* __restrict__ st, int n, double dt, const double x[3], const double v[3], double a[3]) {
+    const double kappa = st->kappa, beta = st->beta, mu = st->mu, h = st->h, dt2 = dt * dt;
+    bool hit = false;
+    a[0] = a[1] = a[2] = 0.0;
+    for (int c = 0; c < n; c++) {
+        const pn_contact_collider* col = st->c + c;
+        const int type = col->type;
+        if (type < PN_CONTACT_PLANE || type > PN_CONTACT_CONTAINER) continue;
+        double nh[3], d;
+        const double r0 = x[0] - col->p[0], r1 = x[1] - col->p[1], r2 = x[2] - col->p[2];
+        if (type == PN_CONTACT_PLANE) {
+            nh[0] = col->n[0]; nh[1] = col->n[1]; nh[2] = col->n[2];
+            d = nh[0] * r0 + nh[1] * r1 + nh[2] * r2;
+        } else {
+            const double L = sqrt(r0 * r0 + r1 * r1 + r2 * r2);
+            if (L > 0.0) {
+                nh[0] = r0 / L; nh[1] = r1 / L; nh[2] = r2 / L;
+            } else {
+                nh[0] = 0.0; nh[1] = 1.0; nh[2] = 0.0;
+            }
+            d = L - col->R;
+            if (type == PN_CONTACT_CONTAINER) {
+                d = -d;
+                nh[0] = -nh[0]; nh[1] = -nh[1]; nh[2] = -nh[2];
+            }
+        }
+        const double delta = h - d;
+        if (!(delta > 0.0)) continue;
+        hit = true;
+        const double w0 = v[0] - col->v[0], w1 = v[1] - col->v[1], w2 = v[2] - col->v[2];
+        const double wn = w0 * nh[0] + w1 * nh[1] + w2 * nh[2];
+        const double t0 = w0 - wn * nh[0], t1 = w1 - wn * nh[1], t2 = w2 - wn * nh[2];
+        const double an = (kappa * delta + beta * fmin(fmax(-wn, 0.0) * dt, delta)) / dt2;
+        a[0] += an * nh[0]; a[1] += an * nh[1]; a[2] += an * nh[2];
+        const double wt = sqrt(t0 * t0 + t1 * t1 + t2 * t2);
+        if (wt > 0.0) {
+            const double at = fmin(mu * an, wt / dt), s = at / wt;
+            a[0] -= s * t0; a[1] -= s * t1; a[2] -= s * t2;
+        }
+    }
+    return hit;
+}
+
+// A point's position and velocity (pn_ip_row_acc over its 8 kernels, slots 0..7 one after the other, fp64, not rounded to fp32), then the law.  Returns
+// whether the point is in contact; a = 0 when it is not.
+__device__ __forceinline__ bool pn_contact_point(int p, int n_k, const pn_contact_state* __restrict__ st, int n, double dt, const double* __restrict__ dof,
+                                                 const double* __restrict__ dof_vel, const int* __restrict__ topo, const double* __restrict__ Nx, double a[3]) {
+    double x[3] = {0.0, 0.0, 0.0}, v[3] = {0.0, 0.0, 0.0};
+    a[0] = a[1] = a[2] = 0.0;
+    for (int i = 0; i < 8; i++) {
+        const int k = topo[p * 8 + i];
+        if ((unsigned)k >= (unsigned)n_k) return false;  // never with the tables solver.py builds; keeps every read inside its buffer
+        const double* S = Nx + ((size_t)p * 8 + i) * 10;
+        pn_ip_row_acc(dof + (size_t)k * 30, S, x[0], x[1], x[2]);
+        pn_ip_row_acc(dof_vel + (size_t)k * 30, S, v[0], v[1], v[2]);
+    }
+    if (pn_contact_law(st, n, dt, x, v, a)) return true;
+    a[0] = a[1] = a[2] = 0.0;
+    return false;
+}
+
+// ------------------------------------------------------------------------------------------------ the law at every point (first of two launches)
+// One thread per integration point: accel[p] = a_p, zeros for a point not in contact and for every point of an inactive or empty state.
+#define PN_CONTACT_POINT_THREADS 64   // 3 576 points on the chair: 56 workgroups of one wave, spread over the CUs
+__global__ void __launch_bounds__(PN_CONTACT_POINT_THREADS) k_contact_points(int n_k, int n_IP, const pn_contact_state* __restrict__ st, double dt,
+                                                                             const double* __restrict__ dof, const double* __restrict__ dof_vel,
+                                                                             const int* __restrict__ topo, const double* __restrict__ Nx,
+                                                                             double* __restrict__ accel) {
+    const int p = blockIdx.x * PN_CONTACT_POINT_THREADS + threadIdx.x;
+    if (p >= n_IP) return;
+    const int n = min(st->n, PN_CONTACT_SLOTS);
+    double a[3] = {0.0, 0.0, 0.0};
+    if (st->active != 0 && n > 0) pn_contact_point(p, n_k, st, n, dt, dof, dof_vel, topo, Nx, a);
+    accel[(size_t)p * 3] = a[0]; accel[(size_t)p * 3 + 1] = a[1]; accel[(size_t)p * 3 + 2] = a[2];
+}
+
+// ------------------------------------------------------------------------------------------------ the right-hand side, every substep
+// One workgroup of four waves per GMLS kernel.  Thread t takes the entries t, t + 256, ... of the kernel's run (kernel_bg / kernel_cnt / buffer: the
+// (point, slot) pairs, ascending) in ascending order and adds m Nx[point, slot, j] a[r] into 30 sums, a = the point's contact acceleration: read from
+// `accel` (written by k_contact_points in the launch before this one), or with FUSED evaluated here by the same pn_contact_point — 8 x redundant across
+// a point's kernels, but one launch; every workgroup that evaluates a point runs the same code on the same inputs, so all agree on it to the bit.
+// Each wave adds its lanes by the shuffle tree 32, 16 ... 1, lane 0 of each wave puts its totals into LDS, and the 30 threads that write add the
+// waves in the order ((w0 + w1) + w2) + w3.  No atomics; the order is a function of the run alone.  A kernel none of whose points has a != 0, and so
+// every kernel of an inactive or empty state, copies rhs_in's bits (g + 0.0 would turn a -0.0 into +0.0).
+template <bool FUSED>
+__global__ void __launch_bounds__(PN_CONTACT_THREADS) k_contact_rhs(int n_k, int n_IP, const pn_contact_state* __restrict__ st, double dt, double dx3,
+                                                                    const double* __restrict__ dof, const double* __restrict__ dof_vel,
+                                                                    const int* __restrict__ topo, const double* __restrict__ rho,
+                                                                    const double* __restrict__ Nx, const int* __restrict__ kernel_bg,
+                                                                    const int* __restrict__ kernel_cnt, const int* __restrict__ buffer,
+                                                                    const double* __restrict__ Nx_csr, const double* __restrict__ rhs_in,
+                                                                    double* __restrict__ rhs_out, const double* __restrict__ accel) {
+    __shared__ double s_part[PN_CONTACT_WAVES][30];
+    const int kid = blockIdx.x, t = threadIdx.x;
+    const int bg = min(max(kernel_bg[kid], 0), 8 * n_IP), end = min(bg + max(kernel_cnt[kid], 0), 8 * n_IP);
+    const double* g = rhs_in + (size_t)kid * 30;
+    double* o = rhs_out + (size_t)kid * 30;
+    int n = 0;
+    bool on = true;
+    if (FUSED) {
+        n = min(st->n, PN_CONTACT_SLOTS);
+        on = st->active != 0 && n > 0;  // uniform over the launch
+    }
+    double acc[30];
+#pragma unroll
+    for (int i = 0; i < 30; i++) acc[i] = 0.0;
+    int hit = 0;
+    if (on) {
+        for (int e = bg + t; e < end; e += PN_CONTACT_THREADS) {
+            const int p = buffer[e] >> 3;
+            if ((unsigned)p >= (unsigned)n_IP) continue;  // never with the tables solver.py builds; keeps every read inside its buffer
+            double a[3];
+            if (FUSED) {
+                pn_contact_point(p, n_k, st, n, dt, dof, dof_vel, topo, Nx, a);
+            } else {
+                a[0] = accel[(size_t)p * 3]; a[1] = accel[(size_t)p * 3 + 1]; a[2] = accel[(size_t)p * 3 + 2];
+            }
+            if (a[0] == 0.0 && a[1] == 0.0 && a[2] == 0.0) continue;  // not in contact (a penetrated collider always pushes: a_n > 0)
+            hit = 1;
+            const double m = rho[p] * dx3;
+            const double* N = Nx_csr + (size_t)e * 10;
+#pragma unroll
+            for (int b = 0; b < 10; b++) {
+                const double w = m * N[b];
+#pragma unroll
+                for (int c = 0; c < 3; c++) acc[b * 3 + c] += w * a[c];
+            }
+        }
+    }
+    if (!__syncthreads_or(hit)) {  // uniform over the workgroup
+        if (t < 30) o[t] = g[t];
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < 30; i++) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) acc[i] += __shfl_down(acc[i], off);
+    }
+    if ((t & 63) == 0) {
+#pragma unroll
+        for (int i = 0; i < 30; i++) s_part[t >> 6][i] = acc[i];
+    }
+    __syncthreads();
+    if (t < 30) {
+        double s = s_part[0][t];
+#pragma unroll
+        for (int w = 1; w < PN_CONTACT_WAVES; w++) s += s_part[w][t];
+        o[t] = g[t] + s;
+    }
+}
+
+extern "C" uint64_t pn_sim_contact_bytes(void) { return sizeof(pn_contact_state); }
+
+extern "C" int pn_sim_contact_rhs(int n_k, int n_IP, const void* state, double dt, double dx, const double* dof, const double* dof_vel, const int* topo,
+                                  const double* rho, const double* Nx, const int* kernel_bg, const int* kernel_cnt, const int* buffer,
+                                  const double* Nx_csr, const double* rhs_in, double* rhs_out, double* accel_out, void* stream) {
+    PN_REQUIRE(n_k > 0 && n_IP > 0 && n_IP <= (1 << 27) && state && dof && dof_vel && topo && rho && Nx && kernel_bg && kernel_cnt && buffer && Nx_csr);
+    PN_REQUIRE(rhs_in && rhs_out && rhs_in != rhs_out);
+    PN_REQUIRE(isfinite(dt) && dt > 0.0 && isfinite(dx) && dx > 0.0);
+    const pn_contact_state* st = (const pn_contact_state*)state;
+    const double dx3 = pow(dx, 3.0);
+    hipStream_t s = (hipStream_t)stream;
+    if (accel_out) {  // two launches, the measured faster form: the law once per point, then the per-kernel sums
+        k_contact_points<<<pn_div_up(n_IP, PN_CONTACT_POINT_THREADS), PN_CONTACT_POINT_THREADS, 0, s>>>(n_k, n_IP, st, dt, dof, dof_vel, topo, Nx, accel_out);
+        PN_LAUNCH_CHECK();
+        k_contact_rhs<false><<<n_k, PN_CONTACT_THREADS, 0, s>>>(n_k, n_IP, st, dt, dx3, dof, dof_vel, topo, rho, Nx, kernel_bg, kernel_cnt, buffer, Nx_csr,
+                                                                 rhs_in, rhs_out, accel_out);
+    } else {  // one launch: every entry evaluates its point itself
+        k_contact_rhs<true><<<n_k, PN_CONTACT_THREADS, 0, s>>>(n_k, n_IP, st, dt, dx3, dof, dof_vel, topo, rho, Nx, kernel_bg, kernel_cnt, buffer, Nx_csr,
+                                                                rhs_in, rhs_out, nullptr);
+    }
+    PN_LAUNCH_CHECK();
+    return PN_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ host-side updates
+struct PnContactParams {
+    int active, set;
+    double p[4];
+};
+
+__global__ void k_contact_params(pn_contact_state* __restrict__ st, PnContactParams s) {
+    if (s.active >= 0) st->active = s.active;
+    if (s.set) {
+        st->kappa = s.p[0]; st->beta = s.p[1]; st->mu = s.p[2]; st->h = s.p[3];
+    }
+}
+
+extern "C" int pn_sim_contact_set_params(void* state, int active, const double* params4_host, void* stream) {
+    PN_REQUIRE(state && active >= -1 && active <= 1);
+    PnContactParams s;
+    s.active = active; s.set = params4_host != nullptr;
+    for (int i = 0; i < 4; i++) {
+        s.p[i] = params4_host ? params4_host[i] : 0.0;
+        PN_REQUIRE(isfinite(s.p[i]));
+    }
+    if (params4_host) {  // dt^2 a_n <= (kappa + beta) delta: with these ranges no step pushes a point further out than it was in
+        PN_REQUIRE(s.p[0] > 0.0 && s.p[0] <= 1.0);
+        PN_REQUIRE(s.p[1] >= 0.0 && s.p[1] <= 1.0);
+        PN_REQUIRE(s.p[2] >= 0.0 && s.p[3] >= 0.0);
+    }
+    k_contact_params<<<1, 1, 0, (hipStream_t)stream>>>((pn_contact_state*)state, s);
+    PN_LAUNCH_CHECK();
+    return PN_OK;
+}
+
+struct PnContactSlot {
+    int index, type;
+    double g[10];
+};
+
+// writes the slot, then n = 1 + the highest slot in use: the launch visits the slots 0 .. n-1 and skips the empty ones
+__global__ void k_contact_collider(pn_contact_state* __restrict__ st, PnContactSlot s) {
+    pn_contact_collider* c = st->c + s.index;
+    c->type = s.type; c->reserved = 0;
+    for (int i = 0; i < 3; i++) { c->p[i] = s.g[i]; c->n[i] = s.g[3 + i]; c->v[i] = s.g[7 + i]; }
+    c->R = s.g[6];
+    int n = 0;
+    for (int i = 0; i < PN_CONTACT_SLOTS; i++)
+        if (st->c[i].type != PN_CONTACT_EMPTY) n = i + 1;
+    st->n = n;
+}
+
+extern "C" int pn_sim_contact_set_collider(void* state, int index, int type, const double* geom10_host, void* stream) {
+    PN_REQUIRE(state && index >= 0 && index < PN_CONTACT_SLOTS && type >= PN_CONTACT_EMPTY && type <= PN_CONTACT_CONTAINER);
+    PN_REQUIRE(type == PN_CONTACT_EMPTY || geom10_host);
+    PnContactSlot s;
+    s.index = index; s.type = type;
+    for (int i = 0; i < 10; i++) {
+        s.g[i] = (type != PN_CONTACT_EMPTY && geom10_host) ? geom10_host[i] : 0.0;
+        PN_REQUIRE(isfinite(s.g[i]));
+    }
+    if (type == PN_CONTACT_PLANE) PN_REQUIRE(fabs(s.g[3] * s.g[3] + s.g[4] * s.g[4] + s.g[5] * s.g[5] - 1.0) <= 1e-9);  // a unit normal
+    if (type == PN_CONTACT_SPHERE || type == PN_CONTACT_CONTAINER) PN_REQUIRE(s.g[6] > 0.0);
+    k_contact_collider<<<1, 1, 0, (hipStream_t)stream>>>((pn_contact_state*)state, s);
+    PN_LAUNCH_CHECK();
+    return PN_OK;
+}

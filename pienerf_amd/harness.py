@@ -183,6 +183,7 @@ class SimRenderHarness:
         self._graph_done = None
         self._graph_drag = self.sim.drag_enabled   # the substep's k_drag_force launch is in the graph or it is not
         self._graph_pins = self.sim.pin_enabled    # ... and so is its k_pin_rhs launch (Simulator.enable_pin_motion)
+        self._graph_contact = self.sim.contact_enabled   # ... and its contact launches (Simulator.enable_contact)
         self._graph_form_epoch = self._net_form_epoch()
         return self
 
@@ -202,6 +203,11 @@ class SimRenderHarness:
         if self.sim.pin_enabled and not captured:
             raise RuntimeError(f"pin motion: {what} was captured before enable_pin_motion(), its substep ignores the pin motion: {again} again")
 
+    def _check_contact_captured(self, captured, what, again):
+        """Colliders and parameters changed after a capture need no recapture (the state is device memory); the launch itself must be in the graph."""
+        if self.sim.contact_enabled and not captured:
+            raise RuntimeError(f"contact: {what} was captured before enable_contact(), its substep ignores the colliders: {again} again")
+
     @torch.no_grad()
     def step_graph(self, pose=None):
         """Replays the captured step.  Outputs are static tensors (overwritten by the next replay); they are complete — including frames
@@ -210,6 +216,7 @@ class SimRenderHarness:
             self.capture()
         self._check_net_form(self._graph_form_epoch, "the step")
         self._check_pins_captured(self._graph_pins, "the step graph", "capture()")
+        self._check_contact_captured(self._graph_contact, "the step graph", "capture()")
         self._check_previous_graph_frame()
         if pose is not None:
             self._graph_pose.copy_(torch.from_numpy(np.asarray(pose, np.float32)).unsqueeze(0))
@@ -306,6 +313,7 @@ class SimRenderHarness:
         self.sim.force_hooks = (self._pipe.before_force, self._pipe.after_force) if self._pipe.sim_on_lanes else None
         self._pipe_drag = self.sim.drag_enabled
         self._pipe_pins = self.sim.pin_enabled
+        self._pipe_contact = self.sim.contact_enabled
         self._drag_frame = ("pipelined",)
         self._pipe_backend = be
         self._pipe_form_epoch = self._net_form_epoch()
@@ -320,6 +328,7 @@ class SimRenderHarness:
     def step_pipelined(self, pose=None):
         self._check_net_form(self._pipe_form_epoch, "the pipeline")
         self._check_pins_captured(self._pipe_pins, "the pipeline", "capture_pipelined()")
+        self._check_contact_captured(self._pipe_contact, "the pipeline", "capture_pipelined()")
         out = self._pipe.step(pose)
         self.frame = self._pipe.frame
         return out

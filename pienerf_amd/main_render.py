@@ -4,6 +4,8 @@ deformed point cloud and the per-frame IP state the reference's ``main_render.py
 
     python -m pienerf_amd.main_render --frames 30 --out output_img/chair [--ply model/chair_0.ply] [--ckpt ws/checkpoints/ngp_ep0300.pth]
            [--W 800 --H 800] [--radius 5 --azimuth 0 --elevation 0 --fovy 50] [--force fx fy fz | --drag X0 Y0 X1 Y1] [--pin_shake AX AY AZ HZ] [--pin_twist NX NY NZ DEG HZ [--pin_centre X Y Z]] [--save_ply] [--save_ip_state]
+           [--floor Y] [--collide_sphere CX CY CZ R]... [--collide_inside CX CY CZ R] [--contact_stiffness 0.5 --contact_damping 0.5 --friction 0.5
+           --contact_thickness DX/2] [--unpin]
            [--save_mesh [--mesh_resolution 128] [--mesh_threshold 10] [--mesh_con 0] [--mesh_normals] [--mesh_color]]
 
 Without --ply / --ckpt the synthetic chair of pienerf_amd.scene is used (there are no assets on the GPU box).
@@ -12,6 +14,9 @@ by its GMLS field before every frame's substep, as OUT/mesh_{f}.ply with the sam
 --pin_shake / --pin_twist move the pinned points of the cloud (Simulator.enable_pin_motion): a sinusoidal translation with amplitude (AX, AY, AZ) at HZ,
 a rotation about the axis (NX, NY, NZ) through --pin_centre (default: the pins' centroid) by DEG sin(2 pi HZ t) degrees; they compose with each other and
 with --force / --drag, and images, --save_ply and --save_mesh follow the moving object.
+--floor / --collide_sphere / --collide_inside give the object something to meet (Simulator.enable_contact): a floor at height Y, solid
+spheres (repeatable), a container sphere the object stays inside; --unpin clears every pin of the cloud, so the object can be dropped.  They compose with
+--force, --drag, --pin_*, --save_ply and --save_mesh.
 Without --ckpt such a run renders and meshes the SHAPED synthetic checkpoint (its density field has the solid's shape; the plain one's does not).
 Reference: main_gui.py:20-66 (model + simulator construction), nerf/gui.py:556-645 (test_step: IP info -> substep -> render),
 main_render.py:47-104 (frame loop, save_image), simulator/solver.py:109-113 (OutputToPly).
@@ -32,6 +37,9 @@ def build_harness(args):
                             max_iter_num=args.max_iter_num, num_seek_IP=args.num_seek_IP, bound=args.bound, dt_gamma=args.dt_gamma,
                             max_steps=args.max_steps, T_thresh=args.T_thresh, bg_radius=args.bg_radius)
     cloud = scene.cloud_from_ply(args.ply) if args.ply else None
+    if args.unpin:   # every pin of the loaded cloud cleared: nothing holds the object (drop it onto --floor)
+        cloud = dict(cloud if cloud is not None else scene.make_chair_points(hgs=opt["hash_grid_size"], bound=opt["bound"]))
+        cloud["pin"] = np.zeros_like(np.asarray(cloud["pin"]))
     ckpt = None
     if args.save_mesh and not args.ckpt:   # a density field with the solid's shape, as python -m pienerf_amd.mesh uses: the plain synthetic field has no surface
         ckpt = scene.make_checkpoint(bound=args.bound, shaped=True, bg_radius=args.bg_radius)
@@ -59,6 +67,33 @@ def bind_rest_mesh(h, args):
     return binding, triangles, colors
 
 
+def wants_contact(args):
+    return args.floor is not None or bool(args.collide_sphere) or args.collide_inside is not None
+
+
+def configure_contact(sim, args):
+    """--floor / --collide_sphere / --collide_inside and the contact parameters as calls on `sim`; returns the colliders' indices.  Nothing is called
+    without a collider argument."""
+    if not wants_contact(args):
+        if any(v is not None for v in (args.contact_stiffness, args.contact_damping, args.friction, args.contact_thickness)):
+            raise SystemExit("--contact_stiffness / --contact_damping / --friction / --contact_thickness need --floor, --collide_sphere or --collide_inside")
+        return []
+    d = lambda v, dflt: dflt if v is None else v
+    ids = []
+    try:
+        sim.enable_contact(stiffness=d(args.contact_stiffness, 0.5), damping=d(args.contact_damping, 0.5), friction=d(args.friction, 0.5),
+                           thickness=args.contact_thickness)
+        if args.floor is not None:
+            ids.append(sim.add_plane((0.0, args.floor, 0.0), (0.0, 1.0, 0.0)))
+        for c in args.collide_sphere or []:
+            ids.append(sim.add_sphere(c[:3], c[3]))
+        if args.collide_inside is not None:
+            ids.append(sim.add_sphere(args.collide_inside[:3], args.collide_inside[3], inside=True))
+    except ValueError as e:   # a parameter out of range, a radius <= 0, a ninth collider
+        raise SystemExit(f"contact: {e}")
+    return ids
+
+
 def run(args):
     if args.pin_centre is not None and args.pin_twist is None:
         raise SystemExit("--pin_centre is the centre of --pin_twist")
@@ -81,6 +116,7 @@ def run(args):
                                  rotate=(tw[:3], tw[3], tw[4], 0.0, args.pin_centre) if tw is not None else None)
         except ValueError as e:   # a cloud without pinned points, a zero axis, a non-finite value
             raise SystemExit(f"--pin_shake / --pin_twist: {e}")
+    configure_contact(h.sim, args)
     if args.save_mesh:
         binding, triangles, colors = bind_rest_mesh(h, args)
         if not args.quiet:
@@ -115,6 +151,8 @@ def run(args):
             h.synchronize()
             h.sim.OutputToPly(os.path.join(args.out, f"points_{f}.ply"))
     h.synchronize()
+    if h.sim.contact_enabled and not args.quiet:
+        print(f"contact: {h.sim.contact_count()} of {h.sim.n_IP} integration points in contact in the last substep")
     if not args.quiet:
         print(f"{args.frames} frames -> {os.path.abspath(args.out)} in {time.time() - t0:.2f} s; last frame: {h.model.last_stats}")
     return written
@@ -153,6 +191,15 @@ def parser():
     ap.add_argument("--pin_twist", type=float, nargs=5, default=None, metavar=("NX", "NY", "NZ", "DEG", "HZ"),
                     help="rotate the pinned points about the axis (NX, NY, NZ) by DEG sin(2 pi HZ t) degrees")
     ap.add_argument("--pin_centre", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"), help="a point on --pin_twist's axis (default: the pins' centroid)")
+    ap.add_argument("--floor", type=float, default=None, metavar="Y", help="a floor at height Y for the object to land on (contact, DESIGN.md 4.10)")
+    ap.add_argument("--collide_sphere", type=float, nargs=4, action="append", default=None, metavar=("CX", "CY", "CZ", "R"),
+                    help="a solid sphere the object collides with; repeatable")
+    ap.add_argument("--collide_inside", type=float, nargs=4, default=None, metavar=("CX", "CY", "CZ", "R"), help="a container sphere the object stays inside")
+    ap.add_argument("--contact_stiffness", type=float, default=None, help="share of a penetration removed per substep, in (0, 1] (default 0.5)")
+    ap.add_argument("--contact_damping", type=float, default=None, help="share of the approach velocity removed per substep, in [0, 1] (default 0.5)")
+    ap.add_argument("--friction", type=float, default=None, help="Coulomb friction coefficient of the colliders, >= 0 (default 0.5)")
+    ap.add_argument("--contact_thickness", type=float, default=None, help="contact begins this far outside a collider (default: sim_dx / 2)")
+    ap.add_argument("--unpin", action="store_true", help="clear every pin of the cloud: the object falls (give it a --floor)")
     ap.add_argument("--save_ply", action="store_true")
     ap.add_argument("--save_ip_state", action="store_true")
     ap.add_argument("--save_mesh", action="store_true", help="write the deforming surface mesh of every frame as OUT/mesh_{f}.ply (rest mesh bound to the simulator, "

@@ -38,6 +38,82 @@ DRAG_SCALE_MIN, DRAG_SCALE_MAX = 1e-3, 5e1   # gui.py:865
 PIN_STATE_DOUBLES = 16   # pn_pin_motion (include/pienerf_hip.h) as doubles: 128 bytes = pn_sim_pins_bytes(), checked in _alloc_pins
 
 
+CONTACT_SLOTS = 8          # pn_contact_state's collider slots (include/pienerf_hip.h: PN_CONTACT_SLOTS)
+CONTACT_EMPTY, CONTACT_PLANE, CONTACT_SPHERE, CONTACT_CONTAINER = 0, 1, 2, 3
+# pn_contact_collider / pn_contact_state (include/pienerf_hip.h) as numpy records: 88 and 744 bytes = pn_sim_contact_bytes(), checked in _alloc_contact
+CONTACT_COLLIDER_DTYPE = np.dtype([("type", "<i4"), ("reserved", "<i4"), ("p", "<f8", (3,)), ("n", "<f8", (3,)), ("R", "<f8"), ("v", "<f8", (3,))])
+CONTACT_STATE_DTYPE = np.dtype([("active", "<i4"), ("n", "<i4"), ("kappa", "<f8"), ("beta", "<f8"), ("mu", "<f8"), ("h", "<f8"),
+                                ("c", CONTACT_COLLIDER_DTYPE, (CONTACT_SLOTS,))])
+CONTACT_STATE_DOUBLES = CONTACT_STATE_DTYPE.itemsize // 8
+
+
+def _vec3(v, what):
+    a = np.asarray(v, npfloat)
+    if a.size != 3 or not np.isfinite(a).all():
+        raise ValueError(f"contact: {what} is a finite 3-vector, got {v!r}")
+    return a.reshape(3).copy()
+
+
+def contact_params(stiffness, damping, friction, thickness):
+    """(kappa, beta, mu, h) of pn_sim_contact_set_params, checked: the system matrix is at least M / dt^2, so a point's response to its own contact term
+    is at most (kappa + beta) times its penetration, and with kappa in (0, 1], beta in [0, 1] no step pushes a point further out than it was in;
+    mu >= 0, h >= 0, everything finite.  ValueError otherwise."""
+    p = np.array([float(stiffness), float(damping), float(friction), float(thickness)])
+    if not np.isfinite(p).all():
+        raise ValueError(f"contact: every parameter must be finite, got {p.tolist()}")
+    if not 0.0 < p[0] <= 1.0:
+        raise ValueError(f"contact: stiffness must be in (0, 1], got {p[0]!r}")
+    if not 0.0 <= p[1] <= 1.0:
+        raise ValueError(f"contact: damping must be in [0, 1], got {p[1]!r}")
+    if p[2] < 0.0:
+        raise ValueError(f"contact: friction must be >= 0, got {p[2]!r}")
+    if p[3] < 0.0:
+        raise ValueError(f"contact: thickness must be >= 0, got {p[3]!r}")
+    return p
+
+
+def contact_plane(point, normal, velocity=None):
+    """(type, geom10 = (p, n, R, v)) of pn_sim_contact_set_collider for the plane through `point` with `normal` out of the solid, normalised here once.
+    ValueError for a zero or non-finite normal."""
+    n = _vec3(normal, "a plane's normal")
+    L = float(np.linalg.norm(n))
+    if not (np.isfinite(L) and L > 0.0):
+        raise ValueError(f"contact: a plane's normal must be a nonzero vector, got {normal!r}")
+    g = np.zeros(10)
+    g[0:3], g[3:6] = _vec3(point, "a plane's point"), n / L
+    g[7:10] = _vec3(velocity, "a collider's velocity") if velocity is not None else 0.0
+    return CONTACT_PLANE, g
+
+
+def contact_sphere(centre, radius, inside=False, velocity=None):
+    """(type, geom10) for a solid sphere, or with inside=True the container sphere the object lives in.  ValueError for a radius that is not > 0."""
+    R = float(radius)
+    if not (np.isfinite(R) and R > 0.0):
+        raise ValueError(f"contact: a sphere's radius must be a finite number > 0, got {radius!r}")
+    g = np.zeros(10)
+    g[0:3], g[6] = _vec3(centre, "a sphere's centre"), R
+    g[7:10] = _vec3(velocity, "a collider's velocity") if velocity is not None else 0.0
+    return (CONTACT_CONTAINER if inside else CONTACT_SPHERE), g
+
+
+def pack_contact_state(active, params, colliders):
+    """The bytes of a pn_contact_state (include/pienerf_hip.h) holding `params` = (kappa, beta, mu, h) and `colliders` = CONTACT_SLOTS entries, each
+    None or (type, geom10): what the device state holds after the setters (n = 1 + the highest slot in use)."""
+    st = np.zeros((), CONTACT_STATE_DTYPE)
+    st["active"] = int(active)
+    st["kappa"], st["beta"], st["mu"], st["h"] = (float(v) for v in params)
+    assert len(colliders) == CONTACT_SLOTS
+    n = 0
+    for i, c in enumerate(colliders):
+        if c is None:
+            continue
+        t, g = c
+        st["c"][i]["type"], st["c"][i]["p"], st["c"][i]["n"], st["c"][i]["R"], st["c"][i]["v"] = int(t), g[0:3], g[3:6], g[6], g[7:10]
+        n = i + 1
+    st["n"] = n
+    return st.tobytes()
+
+
 def wheel_force_scale(scale, delta):
     """The GUI's mouse-wheel rule for the drag's force scale (gui.py:857-865): +-0.5 per notch above 1, +-0.1 at or below, clamped to [1e-3, 50]."""
     scale = float(scale)
@@ -141,6 +217,14 @@ class Simulator:
         self.pin_enabled = False
         self._pin_state = self._rhs_ext = self._pin_offsets = None
         self.n_pin = 0
+        # contact with planes and spheres (enable_contact): a pn_contact_state in device memory, read by two launches in front of every substep
+        # (k_contact_points, k_contact_rhs) that write _rhs_contact = (rhs_gravity or _rhs_ext) + the contact term of the state the substep starts from.  The parameters and the
+        # collider slots are mirrored here, so they may be set before initialize() and are uploaded when the state is allocated
+        self.contact_enabled = False
+        self._contact_state = self._rhs_contact = self._contact_accel = None
+        self._contact_params = None
+        self._colliders = [None] * CONTACT_SLOTS
+        self.Nx_csr = None
 
     # ------------------------------------------------------------------ IO (solver.py:109-137)
     def InitializeFromPly(self, path):
@@ -174,6 +258,8 @@ class Simulator:
             self._alloc_drag()
         if self.pin_enabled and self.device.type == "cuda":
             self._alloc_pins()
+        if self.contact_enabled and self.device.type == "cuda":
+            self._alloc_contact()
 
     def precompute(self):
         """Everything of initialize() that is tensor bookkeeping / torch.linalg (device-agnostic), and on a GPU the cell form's work area for the
@@ -253,6 +339,9 @@ class Simulator:
         self.n_pin, self.pin_bg = 0, None   # the pins' tables belong to the layout: built with it when pin motion is enabled, else by enable_pin_motion()
         if self.pin_enabled:
             self._build_pins()
+        self.Nx_csr = None                  # ... and so do the contact launch's: built with the layout when contact is enabled, else by enable_contact()
+        if self.contact_enabled:
+            self._build_contact()
         if self._cells is not None and self.device.type == "cuda":   # a new layout gets a new work area, here and never inside a substep
             self._prepare_cells()
 
@@ -319,6 +408,11 @@ class Simulator:
         self.pin_bg = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(cnt, 0)]).to(torch.int32).contiguous()
         self.pin_of = (order // 8).to(torch.int32).contiguous()
         self.pin_N_csr = self.pin_Nx.reshape(self.n_pin * 8, 10)[order].contiguous()
+
+    def _build_contact(self):
+        """The Nx rows in CSR order (as dNx_csr is for the substep): the contact launch reads a kernel's run as one contiguous stream.  Only with contact
+        enabled.  A new tensor after every precompute(), like the other tables of a layout."""
+        self.Nx_csr = self.IP_Nx.reshape(self.n_IP * 8, 10)[self.buffer.long()].contiguous()
 
     def _prepare_cells(self):
         """The cell form's work area: identity rotations for the warm-started SVD, arrival counters (never inside a stream capture)."""
@@ -452,6 +546,8 @@ class Simulator:
         rhs_g = self.rhs_gravity
         if self.pin_enabled:    # rhs_gravity + the pins' term at THIS substep's time, on the substep's stream, captured with it into graphs
             rhs_g = self._enqueue_pin_rhs()
+        if self.contact_enabled:   # ... + the contact term of THIS substep's state, into a buffer of its own, on the substep's stream, captured with it
+            rhs_g = self._enqueue_contact_rhs(rhs_g)
         if self.persistent and self._coop is not None and 1 <= self.iters <= 32:
             buf, n_wg, plan = self._coop
             check(lib().pn_sim_stepforward_coop(self.n_k, self.n_IP, int(self.iters), float(self.dt), float(self.dx), ptr(self.IP_kernel), ptr(self.IP_mu),
@@ -695,6 +791,160 @@ class Simulator:
     def _pin_clock_restore(self, keep):
         if keep is not None:
             self._pin_state[:1].copy_(keep)
+
+    # ------------------------------------------------------------------ contact with planes and spheres (csrc/pn_contact.hip)
+    def enable_contact(self, stiffness=0.5, damping=0.5, friction=0.5, thickness=None):
+        """From now on every stepforward() first writes rhs + the contact term (csrc/pn_contact.hip: k_contact_points, k_contact_rhs; include/pienerf_hip.h has the law) and
+        runs the substep with it in the rhs_gravity slot: an explicit penalty against the colliders added with add_plane / add_sphere, evaluated at the
+        integration points from the dof / dof_vel that substep starts from; the system matrix and Ainv unchanged.  thickness None: dx / 2 (integration
+        points are cell centres, the visible surface lies about half a cell outside them).  The state lives in device memory, so substeps captured into
+        graphs after this call follow set_collider / set_contact_params without a recapture.  May be called before initialize(); ValueError for
+        parameters out of range (contact_params)."""
+        p = contact_params(stiffness, damping, friction, 0.5 * float(self.dx) if thickness is None else thickness)
+        self._contact_params = p
+        if not self.contact_enabled:
+            if self.dof is not None and self.Nx_csr is None:
+                self._build_contact()
+            self.contact_enabled = True
+            if self.dof is not None and self.device.type == "cuda":
+                self._alloc_contact()
+        elif self._contact_state is not None:
+            self._upload_contact_params()
+        return self
+
+    def _alloc_contact(self):
+        nb = int(lib().pn_sim_contact_bytes())
+        if nb != CONTACT_STATE_DOUBLES * 8:
+            raise RuntimeError(f"libpienerf_hip.so's pn_contact_state has {nb} bytes, solver.py allocates {CONTACT_STATE_DOUBLES * 8}")
+        self._contact_state = torch.zeros(CONTACT_STATE_DOUBLES, dtype=torchfloat, device=self.device)
+        self._rhs_contact = self.rhs_gravity.clone()
+        self._contact_accel = torch.zeros((self.n_IP, 3), dtype=torchfloat, device=self.device)
+        self._upload_contact_params()
+        for i, c in enumerate(self._colliders):
+            if c is not None:
+                self._upload_collider(i)
+
+    def _contact(self):
+        if not self.contact_enabled:
+            raise RuntimeError("Simulator: contact is not enabled (call enable_contact() first)")
+        return self._contact_state
+
+    def _contact_on_gpu(self):
+        st = self._contact()
+        if st is None:
+            raise RuntimeError("Simulator: the contact state lives on a GPU: initialize the simulator on a cuda device first")
+        return st
+
+    def _upload_contact_params(self):
+        p = np.ascontiguousarray(self._contact_params)
+        with self._on_force_stream():
+            check(lib().pn_sim_contact_set_params(ptr(self._contact_state), 1, p.ctypes.data, stream_ptr()), "sim_contact_set_params")
+
+    def _upload_collider(self, i):
+        c = self._colliders[i]
+        t, g = (CONTACT_EMPTY, None) if c is None else (c[0], np.ascontiguousarray(c[1]))
+        with self._on_force_stream():
+            check(lib().pn_sim_contact_set_collider(ptr(self._contact_state), int(i), int(t), g.ctypes.data if g is not None else None, stream_ptr()),
+                  "sim_contact_set_collider")
+
+    def _put_collider(self, i, c):
+        self._colliders[i] = c
+        if self._contact_state is not None:
+            self._upload_collider(i)   # on force_stream: the change lands between two substeps
+        return i
+
+    def _free_slot(self):
+        for i, c in enumerate(self._colliders):
+            if c is None:
+                return i
+        raise ValueError(f"contact: all {CONTACT_SLOTS} collider slots are in use (remove_collider frees one)")
+
+    def set_contact_params(self, stiffness=None, damping=None, friction=None, thickness=None):
+        """New values for the parameters given (None keeps one), from the next substep on.  ValueError for a value out of range."""
+        self._contact()
+        old = self._contact_params
+        new = [o if v is None else v for o, v in zip(old, (stiffness, damping, friction, thickness))]
+        self._contact_params = contact_params(*new)
+        if self._contact_state is not None:
+            self._upload_contact_params()
+
+    def add_plane(self, point, normal, velocity=None):
+        """A half-space: the solid lies behind the plane through `point`, `normal` (normalised here) points out of it.  `velocity` (None: at rest) is the
+        collider's own, for the relative velocity of damping and friction; the plane itself moves only when set_collider moves it.  Returns the
+        collider's index; ValueError for a zero normal or a ninth collider."""
+        self._contact()
+        c = contact_plane(point, normal, velocity)
+        return self._put_collider(self._free_slot(), c)
+
+    def add_sphere(self, centre, radius, inside=False, velocity=None):
+        """A solid sphere, or with inside=True a container the object lives in.  Returns the collider's index; ValueError for radius <= 0 or a ninth
+        collider."""
+        self._contact()
+        c = contact_sphere(centre, radius, inside, velocity)
+        return self._put_collider(self._free_slot(), c)
+
+    def _slot(self, index):
+        self._contact()
+        i = int(index)
+        if not 0 <= i < CONTACT_SLOTS or self._colliders[i] is None:
+            raise ValueError(f"contact: there is no collider {index!r}")
+        return i
+
+    def set_collider(self, index, point=None, normal=None, centre=None, radius=None, inside=None, velocity=None):
+        """Changes collider `index` from the next substep on; what is left None keeps its value.  A plane takes point / normal, a sphere centre / radius /
+        inside, both velocity.  A moving collider is scripted from the host with this, per frame, with `velocity` given for the relative velocity.
+        ValueError for an index without a collider, an argument of the other kind, or a value add_plane / add_sphere would refuse."""
+        i = self._slot(index)
+        t, g = self._colliders[i]
+        vel = g[7:10] if velocity is None else velocity
+        if t == CONTACT_PLANE:
+            if centre is not None or radius is not None or inside is not None:
+                raise ValueError(f"contact: collider {i} is a plane: it takes point, normal and velocity")
+            c = contact_plane(g[0:3] if point is None else point, g[3:6] if normal is None else normal, vel)
+        else:
+            if point is not None or normal is not None:
+                raise ValueError(f"contact: collider {i} is a sphere: it takes centre, radius, inside and velocity")
+            c = contact_sphere(g[0:3] if centre is None else centre, g[6] if radius is None else radius, (t == CONTACT_CONTAINER) if inside is None else inside, vel)
+        self._put_collider(i, c)
+
+    def remove_collider(self, index):
+        """Empties the slot: the collider acts on no further substep, its index may be handed out again."""
+        self._put_collider(self._slot(index), None)
+
+    def clear_colliders(self):
+        self._contact()
+        for i, c in enumerate(self._colliders):
+            if c is not None:
+                self._put_collider(i, None)
+
+    def contact_state_bytes(self):
+        """What the device state holds, packed from the mirror kept here (pack_contact_state): tests compare the device's bytes with it."""
+        self._contact()
+        return pack_contact_state(1, self._contact_params, self._colliders)
+
+    def _enqueue_contact_rhs(self, rhs_in, one_launch=False):
+        """_rhs_contact = rhs_in + the contact term of the current dof / dof_vel, on the current stream.  Returns _rhs_contact.  Two launches: the law at
+        every point into _contact_accel, then the per-kernel sums (the measured faster form).  one_launch=True (tools/time_contact.py, tests):
+        the form in which every entry evaluates its point itself — the same bits in _rhs_contact, _contact_accel left as it is."""
+        check(lib().pn_sim_contact_rhs(self.n_k, self.n_IP, ptr(self._contact_on_gpu()), float(self.dt), float(self.dx), ptr(self.dof), ptr(self.dof_vel),
+                                       ptr(self.IP_kernel), ptr(self.IP_rho), ptr(self.IP_Nx), ptr(self.kernel_bg), ptr(self.kernel_cnt), ptr(self.buffer),
+                                       ptr(self.Nx_csr), ptr(rhs_in), ptr(self._rhs_contact), None if one_launch else ptr(self._contact_accel), stream_ptr()),
+              "sim_contact_rhs")
+        return self._rhs_contact
+
+    def contact_accel(self):
+        """[n_IP, 3]: the contact acceleration a_i of every integration point in the last substep enqueued (zeros for a point not in contact).  The
+        simulator's own buffer, overwritten by the next substep."""
+        self._contact_on_gpu()
+        return self._contact_accel
+
+    def contact_count(self):
+        """Integration points in contact in the last substep (a_i != 0: a penetrated collider always pushes, a_n > 0): contact's one read back to the
+        host.  Like pin_clock() it waits for force_stream (or the current stream) only."""
+        self._contact_on_gpu()
+        s = self.force_stream if self.force_stream is not None else torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(s):
+            return int((self._contact_accel != 0.0).any(dim=1).sum().item())
 
     def bind_points(self, points, normals=None):
         """Binds arbitrary rest-space points [V,3] (the space of IP_pos and of extract_geometry's mesh; taken in fp64) to this simulator: a
