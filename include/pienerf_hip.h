@@ -645,6 +645,43 @@ int pn_sim_contact_rhs(int n_k, int n_IP, const void* state, double dt, double d
                        const double* rho, const double* Nx, const int* kernel_bg, const int* kernel_cnt, const int* buffer, const double* Nx_csr,
                        const double* rhs_in, double* rhs_out, double* accel_out, void* stream);
 
+/* The colliders drawn into a rendered frame (csrc/pn_colliders.hip; NeRFRenderer.set_collider_overlay): one launch behind the frame
+ * driver, a thread per ray, composites the analytic surfaces of a pn_contact_state into `image` with a depth test against the object.  `contact_state`
+ * is DEVICE memory with the pn_contact_state layout (the simulator's own buffer or a 744-byte copy), read at execution time: a captured launch follows
+ * set_collider without a recapture.  The slots 0 .. n-1 that hold a valid type are drawn; `active` is ignored (it switches the force, not the picture).
+ * The fp64 fields are rounded to fp32 once per workgroup; everything per ray is fp32, one rounding per operation, sums left to right.
+ * t is in units of rays_d AS GIVEN (how depth_0 measures it); q = d.d, dh = d / sqrt(q).  Per ray (o, d), over the slots in index order — a later
+ * slot wins only with a strictly smaller t:
+ *     plane (p, nh):     nd = nh.d;  hit iff nd < 0 (front face only) and t = nh.(p - o) / nd lies in (t_min, t_max);  normal nh
+ *     sphere (c, R):     oc = o - c, b = oc.d, disc = b b - q (oc.oc - R R);  hit iff disc > 0;  t = (-b - sqrt(disc)) / q if that is > t_min, else
+ *                        (-b + sqrt(disc)) / q;  then t in (t_min, t_max);  normal (x - c) / R, x = o + t d
+ *     container (c, R):  the larger root only (the inner wall seen through the front: a camera outside still sees the object);  normal -(x - c) / R
+ * Colour of the hit slot k:  shade = ambient + (1 - ambient) |normal.d| / sqrt(q);  for a plane with checker > 0: u = normalised nh x e, e the
+ * coordinate axis on which |nh| is smallest (lowest index on ties), v = nh x u, parity = (floor(u.(x - p) / checker) + floor(v.(x - p) / checker)) & 1,
+ * factor = checker_dim for parity 1, else 1;  c = (rgb[k] factor) shade.
+ * Fade: a = clamp((t_max - t) / (0.5 t_max), 0, 1) — an endless floor dissolves into the background instead of ending at a line.
+ * Composite, with s = weights_sum[i], acc = image[i] on entry (the frame composited over 0), t_obj = depth_0[i] / s when s > 1e-4, else +inf:
+ *     no hit    : out = acc                    cov = s
+ *     t < t_obj : out = a c + (1 - a) acc      cov = a + (1 - a) s        the collider in front of the object
+ *     otherwise : out = acc + ((1 - s) a) c    cov = s + (1 - s) a        the collider behind it
+ *     image[i] = out + (1 - cov) bg_scalar;  coverage_out[i] = cov;  collider_t_out[i] = t, or +inf without a hit
+ * A ray without a hit gets the bits the frame's epilogue writes for the same background: acc + (1 - s) bg, multiply and add rounded separately.
+ * A depth test, not a clamp of the march: exact where the object is opaque at the collider's depth; a collider inside a semi-transparent part of the
+ * object is drawn wholly in front of it or wholly behind.  weights_sum and depth_0 are only read.  The style is a by-value kernel argument: a
+ * captured launch keeps the style it was captured with (changing it needs a recapture). */
+typedef struct pn_collider_style {
+    float rgb[8][3];       /* one colour per slot (PN_CONTACT_SLOTS) */
+    float checker;         /* cell size of a plane's checker pattern in world units; <= 0: no pattern */
+    float checker_dim;     /* factor of the odd cells */
+    float ambient;         /* in [0, 1]: the shade of a surface seen edge-on */
+} pn_collider_style;
+/* rays_o, rays_d [N,3], weights_sum, depth_0 [N], image [N,3] in place; coverage_out, collider_t_out [N] or NULL.  PN_ERR_ARG for a NULL required
+ * pointer, an output overlapping an input, t_max <= t_min, a non-finite scalar or style entry, ambient outside [0, 1], N > (2^31 - 1) / 3.  N == 0:
+ * success, nothing launched.  One launch, 256 threads per workgroup; no atomics, no allocation, no host synchronisation: legal in a stream capture. */
+int pn_draw_colliders(const void* contact_state, const pn_collider_style* style, const float* rays_o, const float* rays_d, uint32_t N, float t_min,
+                      float t_max, float bg_scalar, const float* weights_sum, const float* depth_0, float* image, float* coverage_out,
+                      float* collider_t_out, void* stream);
+
 /* Arbitrary rest-space points carried by the simulator's GMLS field (csrc/pn_warp_points.hip; simulator/binding.py: PointBinding.warp; INTEGRATION.md
  * "Deforming mesh").  Per point p, in fp64: pos = sum_{i<8} sum_{c<10} Nx[p,i,c] dof[topo[p,i] 10 + c, :], rounded to fp32 once.  With normals_out:
  * F[r][j] = sum_i sum_c dNx[p,i,j,c] dof[topo[p,i] 10 + c, r], n' = n0 (f1 x f2) + n1 (f2 x f0) + n2 (f0 x f1) with f_j = column j of F and

@@ -21,6 +21,11 @@ class RenderOpts(C.Structure):
                 ("fused_from", i32), ("fused_whole", i32), ("fused_fold", i32), ("fused_grid", i32)]
 
 
+class ColliderStyle(C.Structure):
+    """pn_collider_style (include/pienerf_hip.h): a by-value argument of the collider overlay's launch."""
+    _fields_ = [("rgb", (f32 * 3) * 8), ("checker", f32), ("checker_dim", f32), ("ambient", f32)]
+
+
 # name -> (restype, argtypes); every function declared in include/pienerf_hip.h
 SIGNATURES = {
     "pn_version": (C.c_char_p, []),
@@ -126,6 +131,7 @@ SIGNATURES = {
     "pn_sim_contact_set_params": (i32, [P, i32, P, P]),
     "pn_sim_contact_set_collider": (i32, [P, i32, i32, P, P]),
     "pn_sim_contact_rhs": (i32, [i32, i32, P, f64, f64, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "pn_draw_colliders": (i32, [P, C.POINTER(ColliderStyle), P, P, u32, f32, f32, f32, P, P, P, P, P, P]),
     "pn_sim_warp_points_group": (i32, []),
     "pn_sim_warp_points": (i32, [i32, i32, P, P, P, P, P, P, P, P]),
     "pn_mc_work_bytes": (u64, [i32, i32, i32]),

@@ -1,0 +1,112 @@
+"""The contact colliders drawn into a rendered frame (csrc/pn_colliders.hip; include/pienerf_hip.h: pn_draw_colliders has the law).
+
+``collider_style`` builds the launch's by-value style; ``draw_colliders_torch`` restates the law in torch ops on the device, the baseline
+tools/time_colliders.py times the HIP launch against (the tests compare the launch with tests/colliders_reference.py's numpy instead).
+"""
+import math
+
+import torch
+
+from ._lib import ColliderStyle
+
+SLOTS = 8
+PLANE, SPHERE, CONTAINER = 1, 2, 3
+PLANE_GREY, OTHER_GREY = 0.8, 0.5   # the default colours: a light grey for a plane's slot, a mid grey for every other
+
+
+def collider_style(rgb=None, types=None, checker=0.0, checker_dim=0.6, ambient=0.35):
+    """A ColliderStyle (pn_collider_style).  `rgb`: colours in slot order, fewer than 8 leave the rest at their defaults — PLANE_GREY for a slot that
+    `types` (8 collider types, 0 = empty; e.g. from Simulator.collider_types()) says holds a plane, OTHER_GREY otherwise.  `checker`: cell size of a
+    plane's checker pattern in world units (<= 0: none), `checker_dim` the factor of its odd cells; `ambient` in [0, 1].  ValueError for a non-finite
+    value, more than 8 colours or ambient outside [0, 1]."""
+    st = ColliderStyle()
+    types = list(types) if types is not None else [0] * SLOTS
+    rgb = [tuple(float(v) for v in c) for c in (rgb or [])]
+    if len(types) != SLOTS or len(rgb) > SLOTS or any(len(c) != 3 for c in rgb):
+        raise ValueError(f"collider_style: at most {SLOTS} colours of 3 components and {SLOTS} types")
+    for k in range(SLOTS):
+        g = PLANE_GREY if types[k] == PLANE else OTHER_GREY
+        c = rgb[k] if k < len(rgb) else (g, g, g)
+        for j in range(3):
+            st.rgb[k][j] = c[j]
+    st.checker, st.checker_dim, st.ambient = float(checker), float(checker_dim), float(ambient)
+    vals = [st.rgb[k][j] for k in range(SLOTS) for j in range(3)] + [st.checker, st.checker_dim, st.ambient]
+    if not all(math.isfinite(v) for v in vals):
+        raise ValueError("collider_style: every value must be finite")
+    if not 0.0 <= st.ambient <= 1.0:
+        raise ValueError(f"collider_style: ambient must be in [0, 1], got {ambient!r}")
+    return st
+
+
+def _dot(a, b):
+    return a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1] + a[..., 2] * b[..., 2]
+
+
+@torch.no_grad()
+def draw_colliders_torch(colliders, style, rays_o, rays_d, t_min, t_max, bg, weights_sum, depth_0, image):
+    """The law in torch ops, fp32, on the device of the rays: (image, coverage, collider_t), nothing in place.  `colliders`: 8 entries, None or
+    (type, geom10) as Simulator keeps them on the host."""
+    o, d, s, acc = rays_o, rays_d, weights_sum, image
+    dev, inf = o.device, float("inf")
+    vec = lambda v: torch.tensor([float(x) for x in v], dtype=torch.float32, device=dev)   # noqa: E731
+    q = _dot(d, d)
+    t_hit = torch.full_like(s, inf)
+    k_hit = torch.full(s.shape, -1, dtype=torch.int64, device=dev)
+    for k, c in enumerate(colliders):
+        if c is None:
+            continue
+        typ, g = c
+        p, n, R = vec(g[0:3]), vec(g[3:6]), float(g[6])
+        if typ == PLANE:
+            nd = _dot(n, d)
+            t = _dot(n, p - o) / nd
+            ok = nd < 0
+        else:
+            oc = o - p
+            b = _dot(oc, d)
+            disc = b * b - q * (_dot(oc, oc) - R * R)
+            ok = disc > 0
+            sq = torch.sqrt(disc.clamp(min=0))
+            t = (-b + sq) / q
+            if typ == SPHERE:
+                t_near = (-b - sq) / q
+                t = torch.where(t_near > t_min, t_near, t)
+        ok = ok & (t > t_min) & (t < t_max)
+        t = torch.where(ok, t, torch.full_like(t, inf))
+        better = t < t_hit
+        k_hit = torch.where(better, torch.full_like(k_hit, k), k_hit)
+        t_hit = torch.where(better, t, t_hit)
+    out, cov = acc.clone(), s.clone()
+    t_obj = torch.where(s > 1e-4, depth_0 / s.clamp(min=1e-30), torch.full_like(s, inf))
+    dn = torch.sqrt(q)
+    for k, c in enumerate(colliders):
+        if c is None:
+            continue
+        typ, g = c
+        p, n, R = vec(g[0:3]), vec(g[3:6]), float(g[6])
+        m = k_hit == k
+        t = torch.where(m, t_hit, torch.zeros_like(t_hit))
+        r = o + t.unsqueeze(-1) * d - p
+        factor = torch.ones_like(t)
+        if typ == PLANE:
+            nd = _dot(n, d)
+            if style.checker > 0:
+                a = [abs(float(v)) for v in n]
+                e = 0 if (a[0] <= a[1] and a[0] <= a[2]) else (1 if a[1] <= a[2] else 2)
+                u = torch.linalg.cross(n, torch.eye(3, device=dev)[e])
+                u = u / u.norm()
+                v = torch.linalg.cross(n, u)
+                cells = torch.floor(_dot(u, r) / style.checker) + torch.floor(_dot(v, r) / style.checker)
+                factor = torch.where(torch.remainder(cells, 2) != 0, torch.full_like(t, style.checker_dim), factor)
+        else:
+            nd = _dot(r / R, d)
+        shade = style.ambient + (1 - style.ambient) * (nd.abs() / dn)
+        col = vec(style.rgb[k]) * (factor * shade).unsqueeze(-1)
+        a = ((t_max - t) / (0.5 * t_max)).clamp(0, 1)
+        front = t < t_obj
+        w = (1 - s) * a
+        o_k = torch.where(front.unsqueeze(-1), a.unsqueeze(-1) * col + (1 - a).unsqueeze(-1) * acc, acc + w.unsqueeze(-1) * col)
+        c_k = torch.where(front, a + (1 - a) * s, s + w)
+        out = torch.where(m.unsqueeze(-1), o_k, out)
+        cov = torch.where(m, c_k, cov)
+    return out + ((1 - cov) * bg).unsqueeze(-1), cov, t_hit

@@ -103,6 +103,7 @@ class SimRenderHarness:
             self._pose_dev = (key, torch.from_numpy(np.asarray(pose, np.float32)).unsqueeze(0).to(self.device))
         rays = get_rays(self._pose_dev[1], intrinsics, H, W, -1)
         m = self.model
+        self._order_overlay_behind_setters()   # before this frame's substep goes onto the simulator's stream: the render still overlaps it
         if simulate:
             main = torch.cuda.current_stream(self.device)
             if self.overlap_sim:
@@ -130,8 +131,10 @@ class SimRenderHarness:
                 out = m.rund_cuda_ops(rays["rays_o"], rays["rays_d"], bg_color=None, perturb=False, **kw)
         if self.sim.drag_enabled:   # what drag() / move() unproject against (only then: without the drag nothing else is kept alive)
             self._drag_frame = ("eager", out["depth_0"].reshape(H, W), m.p_def, pose, intrinsics)
-        return {"image": out["image"].reshape(-1, H, W, 3), "depth": out["depth"].reshape(-1, H, W), "depth_0": out["depth_0"].reshape(-1, H, W),
-                "rays_o": rays["rays_o"], "rays_d": rays["rays_d"]}
+        res = {"image": out["image"].reshape(-1, H, W, 3), "depth": out["depth"].reshape(-1, H, W), "depth_0": out["depth_0"].reshape(-1, H, W),
+               "rays_o": rays["rays_o"], "rays_d": rays["rays_d"]}
+        res.update({k: out[k] for k in ("coverage", "collider_t") if k in out})   # draw_colliders(): the overlay's own outputs
+        return res
 
     # ------------------------------------------------------------------ whole step as one HIP graph
     def _step_body(self, n_trips, W, H):
@@ -151,8 +154,10 @@ class SimRenderHarness:
         main.wait_stream(self._sim_stream)
         # every tensor the graph touches is returned (and so stays referenced): memory freed after capture would go back to the
         # graph's pool and could be handed out again
-        return {"image": out["image"].reshape(-1, H, W, 3), "depth": out["depth"].reshape(-1, H, W), "depth_0": out["depth_0"].reshape(-1, H, W),
-                "weights_sum": out["weights_sum"], "rays_o": rays["rays_o"], "rays_d": rays["rays_d"], "_ip": (IP_pos, IP_F, IP_dF)}
+        res = {"image": out["image"].reshape(-1, H, W, 3), "depth": out["depth"].reshape(-1, H, W), "depth_0": out["depth_0"].reshape(-1, H, W),
+               "weights_sum": out["weights_sum"], "rays_o": rays["rays_o"], "rays_d": rays["rays_d"], "_ip": (IP_pos, IP_F, IP_dF)}
+        res.update({k: out[k] for k in ("coverage", "collider_t") if k in out})   # draw_colliders(): render_continue writes them again
+        return res
 
     @torch.no_grad()
     def capture(self, n_trips=8, W=None, H=None):
@@ -184,6 +189,7 @@ class SimRenderHarness:
         self._graph_drag = self.sim.drag_enabled   # the substep's k_drag_force launch is in the graph or it is not
         self._graph_pins = self.sim.pin_enabled    # ... and so is its k_pin_rhs launch (Simulator.enable_pin_motion)
         self._graph_contact = self.sim.contact_enabled   # ... and its contact launches (Simulator.enable_contact)
+        self._graph_overlay = self.model.collider_overlay_key()   # ... and the render's collider overlay, with its style (draw_colliders)
         self._graph_form_epoch = self._net_form_epoch()
         return self
 
@@ -208,6 +214,41 @@ class SimRenderHarness:
         if self.sim.contact_enabled and not captured:
             raise RuntimeError(f"contact: {what} was captured before enable_contact(), its substep ignores the colliders: {again} again")
 
+    def _check_overlay_captured(self, captured, what, again):
+        """The colliders' state is device memory and is followed without a recapture; the overlay's launch, its style and t_max are in the graph."""
+        now = self.model.collider_overlay_key()
+        if now is not None and captured is None:
+            raise RuntimeError(f"colliders: {what} was captured before draw_colliders(), its frames do not draw the colliders: {again} again")
+        if now != captured:
+            raise RuntimeError(f"colliders: the overlay (its state buffer, style or t_max) changed since {what} was captured: {again} again")
+
+    def draw_colliders(self, style=None, t_max=None):
+        """From the next frame on the renders draw the simulator's colliders (NeRFRenderer.set_collider_overlay on Simulator.collider_state(); DESIGN.md
+        4.11).  `style`: a ColliderStyle (None: pienerf_amd.colliders.collider_style for the colliders present now, no checker).  Call it BEFORE
+        capture() / capture_pipelined(): a graph captured without the launch is refused.  step, capture / step_graph and the single-process
+        capture_pipelined draw them (the pipeline draws the LIVE state: a collider moved by the host can appear up to sim_ahead frames early); the
+        frame-parallel, tile-parallel and staged forms raise while an overlay is set.  ValueError before Simulator.enable_contact()."""
+        from .colliders import collider_style
+        state = self.sim.collider_state()
+        self.model.set_collider_overlay(state, collider_style(types=self.sim.collider_types()) if style is None else style, t_max)
+        return self
+
+    def _order_overlay_behind_setters(self):
+        """set_collider's one-thread launch runs on the simulator's force stream; a frame that draws the colliders reads the state on the render's
+        stream, so with an overlay that stream first waits for what the force stream holds.  Nothing is enqueued without an overlay."""
+        fs = self.sim.force_stream
+        if self.model.collider_overlay_key() is not None and fs is not None:
+            torch.cuda.current_stream(self.device).wait_stream(fs)
+
+    def hide_colliders(self):
+        self.model.clear_collider_overlay()
+        return self
+
+    def _refuse_overlay_form(self, what):
+        if self.model.collider_overlay_key() is not None:
+            raise RuntimeError(f"colliders: {what} does not draw the colliders (the other ranks / ray batches would need the collider state sent with "
+                               "the DOF snapshot): step(), capture() and the single-process capture_pipelined() do; hide_colliders() first")
+
     @torch.no_grad()
     def step_graph(self, pose=None):
         """Replays the captured step.  Outputs are static tensors (overwritten by the next replay); they are complete — including frames
@@ -217,9 +258,11 @@ class SimRenderHarness:
         self._check_net_form(self._graph_form_epoch, "the step")
         self._check_pins_captured(self._graph_pins, "the step graph", "capture()")
         self._check_contact_captured(self._graph_contact, "the step graph", "capture()")
+        self._check_overlay_captured(self._graph_overlay, "the step graph", "capture()")
         self._check_previous_graph_frame()
         if pose is not None:
             self._graph_pose.copy_(torch.from_numpy(np.asarray(pose, np.float32)).unsqueeze(0))
+        self._order_overlay_behind_setters()
         self._graph.replay()
         self._graph_done = torch.cuda.Event()
         self._graph_done.record(torch.cuda.current_stream(self.device))
@@ -288,6 +331,10 @@ class SimRenderHarness:
         import torch.distributed as dist
 
         from .frames import FramePipeline
+        if frame_parallel:
+            self._refuse_overlay_form("the frame-parallel pipeline")
+        if (render_kw or {}).get("ray_batch"):
+            self._refuse_overlay_form("the staged form")
         o = self.opt
         W, H = W or o["W"], H or o["H"]
         on = bool(frame_parallel) and dist.is_available() and dist.is_initialized()
@@ -314,6 +361,8 @@ class SimRenderHarness:
         self._pipe_drag = self.sim.drag_enabled
         self._pipe_pins = self.sim.pin_enabled
         self._pipe_contact = self.sim.contact_enabled
+        self._pipe_overlay = self.model.collider_overlay_key()
+        self._pipe_single = not frame_parallel and not (render_kw or {}).get("ray_batch")
         self._drag_frame = ("pipelined",)
         self._pipe_backend = be
         self._pipe_form_epoch = self._net_form_epoch()
@@ -329,6 +378,9 @@ class SimRenderHarness:
         self._check_net_form(self._pipe_form_epoch, "the pipeline")
         self._check_pins_captured(self._pipe_pins, "the pipeline", "capture_pipelined()")
         self._check_contact_captured(self._pipe_contact, "the pipeline", "capture_pipelined()")
+        if not getattr(self, "_pipe_single", True):
+            self._refuse_overlay_form("the frame-parallel / staged pipeline")
+        self._check_overlay_captured(getattr(self, "_pipe_overlay", None), "the pipeline", "capture_pipelined()")
         out = self._pipe.step(pose)
         self.frame = self._pipe.frame
         return out
@@ -404,6 +456,7 @@ class SimRenderHarness:
         (20 B x N / world per rank over RCCL) gives every rank the whole frame.  Unlike the frame-parallel pipeline, whose throughput is
         capped by the time-sequential simulator, this divides the render LATENCY of a frame by the rank count.  Launches are eager."""
         from .frames import TileParallel
+        self._refuse_overlay_form("the tile-parallel form")
         o, m, dev = self.opt, self.model, self.device
         W, H = W or o["W"], H or o["H"]
         ip = tuple(torch.empty((self.sim.n_IP, c), dtype=torch.float32, device=dev) for c in (3, 9, 27))
@@ -429,6 +482,7 @@ class SimRenderHarness:
     @torch.no_grad()
     def step_tile_parallel(self, pose=None):
         """One sim+render step; every rank gets the full frame: {'image' [1,H,W,3], 'depth' [1,H,W], 'depth_0' [1,H,W]} on the device."""
+        self._refuse_overlay_form("the tile-parallel form")
         if pose is not None:
             self._tile_pose.copy_(torch.from_numpy(np.asarray(pose, np.float32)).view(1, 4, 4).to(self.device))
         full = self._tile.step()

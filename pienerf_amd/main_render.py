@@ -5,7 +5,7 @@ deformed point cloud and the per-frame IP state the reference's ``main_render.py
     python -m pienerf_amd.main_render --frames 30 --out output_img/chair [--ply model/chair_0.ply] [--ckpt ws/checkpoints/ngp_ep0300.pth]
            [--W 800 --H 800] [--radius 5 --azimuth 0 --elevation 0 --fovy 50] [--force fx fy fz | --drag X0 Y0 X1 Y1] [--pin_shake AX AY AZ HZ] [--pin_twist NX NY NZ DEG HZ [--pin_centre X Y Z]] [--save_ply] [--save_ip_state]
            [--floor Y] [--collide_sphere CX CY CZ R]... [--collide_inside CX CY CZ R] [--contact_stiffness 0.5 --contact_damping 0.5 --friction 0.5
-           --contact_thickness DX/2] [--unpin]
+           --contact_thickness DX/2] [--unpin] [--draw_colliders [--collider_color R G B]... [--checker S]]
            [--save_mesh [--mesh_resolution 128] [--mesh_threshold 10] [--mesh_con 0] [--mesh_normals] [--mesh_color]]
 
 Without --ply / --ckpt the synthetic chair of pienerf_amd.scene is used (there are no assets on the GPU box).
@@ -17,6 +17,9 @@ with --force / --drag, and images, --save_ply and --save_mesh follow the moving 
 --floor / --collide_sphere / --collide_inside give the object something to meet (Simulator.enable_contact): a floor at height Y, solid
 spheres (repeatable), a container sphere the object stays inside; --unpin clears every pin of the cloud, so the object can be dropped.  They compose with
 --force, --drag, --pin_*, --save_ply and --save_mesh.
+--draw_colliders draws those colliders into every frame (SimRenderHarness.draw_colliders): a shaded floor with a checker pattern of
+--checker world units (default 2 sim_dx; 0: none) and shaded spheres, depth-tested against the object; --collider_color (repeatable) colours them in slot order
+(the floor first, then the spheres, then the container).  It composes with --bg_radius, --force, --drag, --pin_*, --save_ply and --save_mesh.
 Without --ckpt such a run renders and meshes the SHAPED synthetic checkpoint (its density field has the solid's shape; the plain one's does not).
 Reference: main_gui.py:20-66 (model + simulator construction), nerf/gui.py:556-645 (test_step: IP info -> substep -> render),
 main_render.py:47-104 (frame loop, save_image), simulator/solver.py:109-113 (OutputToPly).
@@ -94,9 +97,35 @@ def configure_contact(sim, args):
     return ids
 
 
+def configure_overlay(h, args):
+    """--draw_colliders / --collider_color / --checker as one call on the harness, behind configure_contact."""
+    if not args.draw_colliders:
+        if args.collider_color or args.checker is not None:
+            raise SystemExit("--collider_color / --checker need --draw_colliders")
+        return None
+    if not wants_contact(args):
+        raise SystemExit("--draw_colliders needs --floor, --collide_sphere or --collide_inside")
+    from .colliders import collider_style
+    try:
+        style = collider_style(rgb=args.collider_color, types=h.sim.collider_types(), checker=2.0 * args.sim_dx if args.checker is None else args.checker)
+    except ValueError as e:
+        raise SystemExit(f"--draw_colliders: {e}")
+    h.draw_colliders(style)
+    return style
+
+
+def check_overlay_args(args):
+    """What configure_overlay refuses, before anything is built."""
+    if args.draw_colliders and not wants_contact(args):
+        raise SystemExit("--draw_colliders needs --floor, --collide_sphere or --collide_inside")
+    if not args.draw_colliders and (args.collider_color or args.checker is not None):
+        raise SystemExit("--collider_color / --checker need --draw_colliders")
+
+
 def run(args):
     if args.pin_centre is not None and args.pin_twist is None:
         raise SystemExit("--pin_centre is the centre of --pin_twist")
+    check_overlay_args(args)
     h = build_harness(args)
     pose = scene.orbit_pose(args.radius, args.azimuth, args.elevation)
     os.makedirs(args.out, exist_ok=True)
@@ -117,6 +146,7 @@ def run(args):
         except ValueError as e:   # a cloud without pinned points, a zero axis, a non-finite value
             raise SystemExit(f"--pin_shake / --pin_twist: {e}")
     configure_contact(h.sim, args)
+    configure_overlay(h, args)
     if args.save_mesh:
         binding, triangles, colors = bind_rest_mesh(h, args)
         if not args.quiet:
@@ -200,6 +230,10 @@ def parser():
     ap.add_argument("--friction", type=float, default=None, help="Coulomb friction coefficient of the colliders, >= 0 (default 0.5)")
     ap.add_argument("--contact_thickness", type=float, default=None, help="contact begins this far outside a collider (default: sim_dx / 2)")
     ap.add_argument("--unpin", action="store_true", help="clear every pin of the cloud: the object falls (give it a --floor)")
+    ap.add_argument("--draw_colliders", action="store_true", help="draw the colliders into every frame (DESIGN.md 4.11); needs --floor, --collide_sphere or --collide_inside")
+    ap.add_argument("--collider_color", type=float, nargs=3, action="append", default=None, metavar=("R", "G", "B"),
+                    help="a collider's colour, in slot order; repeatable (default: a light grey for a plane, a mid grey otherwise)")
+    ap.add_argument("--checker", type=float, default=None, metavar="S", help="cell size of the floor's checker pattern (default: 2 sim_dx; 0: none)")
     ap.add_argument("--save_ply", action="store_true")
     ap.add_argument("--save_ip_state", action="store_true")
     ap.add_argument("--save_mesh", action="store_true", help="write the deforming surface mesh of every frame as OUT/mesh_{f}.ply (rest mesh bound to the simulator, "

@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 
 from .. import raymarching
-from .._lib import RenderOpts, check, lib, ptr, require_gpu, stream_ptr
+from .._lib import ColliderStyle, RenderOpts, check, lib, ptr, require_gpu, stream_ptr
 from .utils import get_pnts_in_grids
 
 
@@ -78,6 +78,7 @@ class NeRFRenderer(nn.Module):
         self._frame = None
         self._frames = {}
         self.last_stats = None
+        self._overlay = None   # set_collider_overlay: (contact state on the device, ColliderStyle, t_max)
 
     def forward(self, x, d):
         raise NotImplementedError()
@@ -100,6 +101,61 @@ class NeRFRenderer(nn.Module):
     @staticmethod
     def _autocast_half():
         return False
+
+    # ------------------------------------------------------------------ the contact colliders drawn into the frame (csrc/pn_colliders.hip)
+    def set_collider_overlay(self, state, style=None, t_max=None):
+        """From now on rund_cuda (render_deformed) and render_continue draw the colliders of `state` into the frame: one launch behind the frame driver
+        (pn_draw_colliders; include/pienerf_hip.h has the law) composites them with a depth test against the object.  `state` is a device tensor of 93
+        doubles with the pn_contact_state layout — Simulator.collider_state() or a copy — read on the device at execution time, so a captured render
+        follows set_collider without a recapture.  `style`: a ColliderStyle (pienerf_amd.colliders.collider_style; None: its defaults), baked into a
+        captured launch: changing it needs a recapture.  `t_max` (None: 8 * bound): the far end of the colliders, in units of rays_d; they fade into
+        the background over its second half.  The returned dict gains 'coverage' and 'collider_t'; 'weights_sum', 'depth' and 'depth_0' stay the
+        object's own.  The static and hierarchical renders and the op-by-op loop raise while an overlay is set."""
+        from ..colliders import collider_style
+        if not (torch.is_tensor(state) and state.dtype == torch.float64 and state.numel() == 93 and state.is_contiguous()):
+            raise ValueError("set_collider_overlay: `state` is a contiguous tensor of 93 doubles (pn_contact_state; Simulator.collider_state())")
+        require_gpu(state)
+        style = collider_style() if style is None else style
+        if not isinstance(style, ColliderStyle):
+            raise ValueError("set_collider_overlay: `style` is a ColliderStyle (pienerf_amd.colliders.collider_style)")
+        t_max = 8.0 * float(self.bound) if t_max is None else float(t_max)
+        if not (math.isfinite(t_max) and t_max > float(self.min_near)):
+            raise ValueError(f"set_collider_overlay: t_max must be a finite number above min_near = {self.min_near}, got {t_max!r}")
+        self._overlay = (state, style, t_max)
+        return self
+
+    def clear_collider_overlay(self):
+        self._overlay = None
+
+    def collider_overlay_key(self):
+        """What a captured render bakes in of the overlay (None without one): the state's address, the style's bytes, t_max."""
+        if self._overlay is None:
+            return None
+        state, style, t_max = self._overlay
+        return (state.data_ptr(), bytes(style), t_max)
+
+    def _refuse_overlay(self, what):
+        if self._overlay is not None:
+            raise RuntimeError(f"collider overlay: {what} does not draw the colliders — only the deformed path does (render_deformed / rund_cuda without "
+                               "perturb, and render_continue); clear_collider_overlay() first")
+
+    def _draw_colliders(self, rays_o, rays_d, bg_scalar, weights_sum, depth_0, image, out, ob=None):
+        """Enqueues the overlay's launch on the current stream, in place in `image` (the frame composited over 0); 'coverage' and 'collider_t' of `out`
+        (then of `ob`, else allocated) receive its other outputs.  Returns (coverage, collider_t)."""
+        state, style, t_max = self._overlay
+        N = image.shape[0]
+        res = []
+        for name in ("coverage", "collider_t"):
+            t = out.get(name) if out is not None else None
+            if t is None and ob is not None:
+                t = ob.get(name)
+            if t is None:
+                t = torch.empty(N, dtype=torch.float32, device=image.device)
+            assert t.shape == (N,) and t.dtype == torch.float32 and t.is_contiguous()
+            res.append(t)
+        check(lib().pn_draw_colliders(ptr(state), C.byref(style), ptr(rays_o), ptr(rays_d), N, float(self.min_near), t_max, float(bg_scalar),
+                                      ptr(weights_sum), ptr(depth_0), ptr(image), ptr(res[0]), ptr(res[1]), stream_ptr()), "draw_colliders")
+        return res
 
     # ------------------------------------------------------------------ entry point (renderer.py:587-599)
     def render_deformed(self, rays_o, rays_d, staged=False, max_ray_batch=4096, **kwargs):
@@ -180,6 +236,7 @@ class NeRFRenderer(nn.Module):
 
     def rund_cuda(self, rays_o, rays_d, dt_gamma=0, bg_color=None, perturb=False, max_steps=1024, T_thresh=1e-2, **kwargs):
         if perturb:
+            self._refuse_overlay("the op-by-op loop (perturb=True)")
             return self.rund_cuda_ops(rays_o, rays_d, dt_gamma, bg_color, perturb, max_steps, T_thresh, **kwargs)
         prefix = rays_o.shape[:-1]
         rays_o, rays_d = _flat_rays(rays_o, rays_d)
@@ -195,7 +252,9 @@ class NeRFRenderer(nn.Module):
         p_def, p_ori, F_IP, dF_IP = self._ip_state(device)
         assert p_def.shape == p_ori.shape and p_ori.shape[0] > 0  # renderer.py:816-817
         n_vtx = p_ori.shape[0]
-        o = self._deformed_opts(dt_gamma, 0.0 if bg_tensor is not None else bg_color, max_steps, T_thresh, kwargs, n_rays=N)
+        overlay = self._overlay is not None
+        # with an overlay the driver composites over 0 as well: the scalar background goes in behind the colliders, in the overlay's launch
+        o = self._deformed_opts(dt_gamma, 0.0 if (bg_tensor is not None or overlay) else bg_color, max_steps, T_thresh, kwargs, n_rays=N)
         ob = kwargs.get("out_buffers")  # extension: caller-owned outputs (the frame pipeline packs image | depth | depth_0 into one buffer -> one D2H)
         if ob is not None:
             image, depth, depth_0, weights_sum = ob["image"], ob["depth"], ob["depth_0"], ob["weights_sum"]
@@ -220,11 +279,18 @@ class NeRFRenderer(nn.Module):
                   "render_deformed")
             if stats is not None:
                 self._set_stats(stats)
+        res = {"depth": depth.view(*prefix), "depth_0": depth_0.view(*prefix), "weights_sum": weights_sum}
+        covered = weights_sum   # what the background is blended with: the object's own opacity, or with an overlay the object's and the colliders'
+        if overlay:
+            covered, res["collider_t"] = self._draw_colliders(rays_o, rays_d, 0.0 if (bg_tensor is not None or self.bg_radius > 0) else bg_color,
+                                                              weights_sum, depth_0, image, None, ob)
+            res["coverage"] = covered
         if self.bg_radius > 0:
-            self.blend_background(rays_o, rays_d, weights_sum, image)   # in place: `image` may be the caller's out_buffers
+            self.blend_background(rays_o, rays_d, covered, image)   # in place: `image` may be the caller's out_buffers
         elif bg_tensor is not None:
-            image = image + (1 - weights_sum).unsqueeze(-1) * bg_tensor
-        return {"depth": depth.view(*prefix), "image": image.view(*prefix, 3), "depth_0": depth_0.view(*prefix), "weights_sum": weights_sum}
+            image = image + (1 - covered).unsqueeze(-1) * bg_tensor
+        res["image"] = image.view(*prefix, 3)
+        return res
 
     def render_continue(self, slot, rays_o, rays_d, out, n_trips=0, dt_gamma=0, bg_color=None, max_steps=1024, T_thresh=1e-2, static=False, **kwargs):
         """Finishes the frame last rendered on workspace `slot` with a fixed trip count that turned out too small (render_status reports
@@ -236,10 +302,13 @@ class NeRFRenderer(nn.Module):
         N = rays_o.shape[0]
         if self.bg_radius > 0:
             bg_color = 0
+        overlay = self._overlay is not None
         if static:
+            self._refuse_overlay("the static render (render_continue with static=True)")
             o = self._static_opts(dt_gamma, 1 if bg_color is None else bg_color, max_steps, T_thresh)
         else:
-            o = self._deformed_opts(dt_gamma, 1 if bg_color is None else bg_color, max_steps, T_thresh, kwargs, n_rays=N)
+            # with an overlay the epilogue rewrites `image` from the driver's accumulator over 0 and the overlay is applied once more, below
+            o = self._deformed_opts(dt_gamma, 0.0 if overlay else (1 if bg_color is None else bg_color), max_steps, T_thresh, kwargs, n_rays=N)
         image, depth, ws = out["image"].view(-1, 3), out["depth"].view(-1), out["weights_sum"].view(-1)
         depth_0 = out["depth_0"].view(-1) if "depth_0" in out else torch.empty_like(depth)
         assert image.is_contiguous() and image.shape[0] == N
@@ -247,8 +316,14 @@ class NeRFRenderer(nn.Module):
         check(lib().pn_render_continue(self._frames[slot][0], self._net_handle(half=bool(o.fp16)), C.byref(o), ptr(rays_o), ptr(rays_d), N,
                                        ptr(self.density_bitfield), ptr(image), ptr(depth), ptr(depth_0), ptr(ws), stats, int(n_trips), int(bool(static)),
                                        stream_ptr()), "render_continue")
+        covered = ws
+        if overlay:
+            if "depth_0" not in out:
+                raise RuntimeError("render_continue: the collider overlay composites against depth_0: pass the dict the deformed render returned")
+            covered, ct = self._draw_colliders(rays_o, rays_d, 0.0 if self.bg_radius > 0 else (1 if bg_color is None else bg_color), ws, depth_0, image, out)
+            out["coverage"], out["collider_t"] = covered, ct
         if self.bg_radius > 0:
-            self.blend_background(rays_o, rays_d, ws, image)
+            self.blend_background(rays_o, rays_d, covered, image)
         if stats is not None:
             self._set_stats(stats)
         return out
@@ -321,6 +396,7 @@ class NeRFRenderer(nn.Module):
                   stable compaction driven by a device-side trip record, with one 16-byte read-back per batch of 8 trips (the reference
                   synchronises the host on every trip, :351-380).  Per-ray background colours and ``perturb`` take the op-by-op loop
                   ``run_cuda_ops`` (same kernels, host-driven)."""
+        self._refuse_overlay("the static render (run_cuda)")
         if not self.training and not perturb and (self.bg_radius > 0 or not torch.is_tensor(bg_color)):
             return self._run_static_fused(rays_o, rays_d, dt_gamma, 1 if bg_color is None else bg_color, max_steps, T_thresh, **kwargs)
         return self.run_cuda_ops(rays_o, rays_d, dt_gamma, bg_color, perturb, force_all_rays, max_steps, T_thresh, **kwargs)
@@ -358,6 +434,7 @@ class NeRFRenderer(nn.Module):
 
     def run_cuda_ops(self, rays_o, rays_d, dt_gamma=0, bg_color=None, perturb=False, force_all_rays=False, max_steps=1024, T_thresh=1e-2, **kwargs):
         """run_cuda op by op on the drop-in ops (the training branch; the eval branch with perturb / tensor backgrounds; parity tests)."""
+        self._refuse_overlay("the static render (run_cuda_ops)")
         shape = rays_o.shape[:-1]
         o3, d3 = rays_o.contiguous().view(-1, 3), rays_d.contiguous().view(-1, 3)
         nears, fars = raymarching.near_far_from_aabb(o3, d3, self.aabb_train if self.training else self.aabb_infer, self.min_near)
@@ -449,6 +526,7 @@ class NeRFRenderer(nn.Module):
                   when bg_radius > 0.  Takes a background of None / a scalar / one colour [3] / one colour per ray [N, 3].
         otherwise (train() mode, autograd recording, perturb, fp16 autocast — there is no half form of the launch —, or
                   num_steps + upsample_steps beyond the launch's LDS-resident limit, pn_hier_max_samples() = 512):  ``run_ops``."""
+        self._refuse_overlay("the hierarchical render (run)")
         self._check_hier_steps(num_steps, upsample_steps)
         if self._hier_fused_ok(rays_o, num_steps, upsample_steps, bg_color, perturb):
             return self._run_hier_fused(rays_o, rays_d, int(num_steps), int(upsample_steps), bg_color)
@@ -479,6 +557,7 @@ class NeRFRenderer(nn.Module):
     def run_ops(self, rays_o, rays_d, num_steps=128, upsample_steps=128, bg_color=None, perturb=False, **kwargs):
         """``run`` as the reference's op sequence on near_far_from_aabb / density / color / sample_pdf and torch ops: differentiable (the training
         branch), with perturb, under autocast, with any background; the parity tests pin it against the reference's own run."""
+        self._refuse_overlay("the hierarchical render (run_ops)")
         self._check_hier_steps(num_steps, upsample_steps)
         prefix = rays_o.shape[:-1]
         rays_o = rays_o.contiguous().view(-1, 3)
@@ -594,6 +673,7 @@ class NeRFRenderer(nn.Module):
 
     # ------------------------------------------------------------------ op-by-op loop (reference structure, renderer.py:755-907)
     def rund_cuda_ops(self, rays_o, rays_d, dt_gamma=0, bg_color=None, perturb=False, max_steps=1024, T_thresh=1e-2, **kwargs):
+        self._refuse_overlay("the op-by-op loop (rund_cuda_ops)")
         dtype = torch.float32
         prefix = rays_o.shape[:-1]
         rays_o = rays_o.contiguous().view(-1, 3)

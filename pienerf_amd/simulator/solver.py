@@ -922,6 +922,18 @@ class Simulator:
         self._contact()
         return pack_contact_state(1, self._contact_params, self._colliders)
 
+    def collider_state(self):
+        """The pn_contact_state on the device (93 doubles), the simulator's own buffer: what the renderer's collider overlay reads
+        (NeRFRenderer.set_collider_overlay; SimRenderHarness.draw_colliders), so a drawn collider is where set_collider last put it.  ValueError before
+        enable_contact()."""
+        if not self.contact_enabled:
+            raise ValueError("collider_state: contact is not enabled (call enable_contact() first)")
+        return self._contact_on_gpu()
+
+    def collider_types(self):
+        """The type of every collider slot (CONTACT_EMPTY / _PLANE / _SPHERE / _CONTAINER), from the host mirror."""
+        return [CONTACT_EMPTY if c is None else int(c[0]) for c in self._colliders]
+
     def _enqueue_contact_rhs(self, rhs_in, one_launch=False):
         """_rhs_contact = rhs_in + the contact term of the current dof / dof_vel, on the current stream.  Returns _rhs_contact.  Two launches: the law at
         every point into _contact_accel, then the per-kernel sums (the measured faster form).  one_launch=True (tools/time_contact.py, tests):
