@@ -194,3 +194,42 @@ def density_grid_update(grid, tmp, decay, density_thresh):
     thresh = min(mean, float(density_thresh))
     bits = np.packbits((grid.reshape(-1) > f(thresh)).reshape(-1, 8), axis=1, bitorder="little").reshape(-1)  # bit i of byte n = cell 8n+i (raymarching.cu:270-292)
     return grid, mean, bits
+
+
+def density_cells_partial(cas, H, bound, rand_coords, rand_pick, noise, grid_cas):
+    """The partial sweep's samples of one cascade (renderer.py:501-516): N uniformly drawn cells (`rand_coords` [N,3] int in [0, H)) followed by N picks
+    from the cascade's occupied cells, `rand_pick` [N] uniform in [0, 1) standing for randint(0, n_occ): j = int(float32(u) * float32(n_occ)), clamped
+    to [0, n_occ - 1].  The occupied list is flatnonzero(grid_cas > 0), ascending (torch.nonzero's order; the device compaction is stable).  Jitter
+    `noise` [2N,3] and cell centres as in density_cells_full.  With no occupied cell the second half of the indices is -1 and its points are zero (the
+    reference raises there).  -> (indices [2N] int32 morton codes, xyzs [2N,3] float32, tmp [H^3] float32 = -1, the cascade's fresh temporary grid)."""
+    from . import morton3D
+    f = np.float32
+    rand_coords = np.asarray(rand_coords, np.int32).reshape(-1, 3)
+    N = rand_coords.shape[0]
+    rand_pick, noise = np.asarray(rand_pick, f).reshape(N), np.asarray(noise, f).reshape(2 * N, 3)
+    occ = np.flatnonzero(np.asarray(grid_cas, f).reshape(-1) > 0)
+    n_occ = len(occ)
+    indices = np.full(2 * N, -1, np.int32)
+    indices[:N] = morton3D(rand_coords)
+    if n_occ > 0:
+        j = (rand_pick * f(n_occ)).astype(np.int64)     # one float32 multiply, truncated
+        indices[N:] = occ[np.clip(j, 0, n_occ - 1)]
+    w, half = _cell_centres(cas, H, bound)
+    live = indices >= 0
+    xyzs = np.zeros((2 * N, 3), f)
+    xyzs[live] = w[indices[live]] + (noise[live] * f(2.0) - f(1.0)) * half
+    return indices, xyzs, np.full(H ** 3, -1, f)
+
+
+def density_scatter(indices, sigmas, tmp_cas):
+    """tmp_grid[cas, indices] = sigmas (renderer.py:527) on a copy of `tmp_cas`; indices of -1 write nothing.  A cell indexed more than once keeps ONE
+    of the values sent to it (here the last in order, numpy's rule; the device keeps whichever store lands last).  -> (tmp, ambiguous [cells] bool:
+    cells that received different values)."""
+    indices, sigmas = np.asarray(indices, np.int64).reshape(-1), np.asarray(sigmas, np.float32).reshape(-1)
+    tmp = np.asarray(tmp_cas, np.float32).copy()
+    live = indices >= 0
+    tmp[indices[live]] = sigmas[live]
+    lo, hi = np.full(tmp.shape, np.inf, np.float32), np.full(tmp.shape, -np.inf, np.float32)
+    np.minimum.at(lo, indices[live], sigmas[live])
+    np.maximum.at(hi, indices[live], sigmas[live])
+    return tmp, hi > lo

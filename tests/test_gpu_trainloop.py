@@ -34,24 +34,11 @@ def test_run_cuda_training_branch_matches_oracle_composition():
     assert int(net.step_counter[0, 0]) == int(rays[:, 2].sum()) and int(net.step_counter[0, 1]) == len(o)
     assert np.abs(out["image"][0].detach().cpu().numpy() - image).max() < 1e-4
     assert np.abs(out["weights_sum"].detach().cpu().numpy() - ws).max() < 1e-4
-    # directional derivative of a scalar loss along a random direction in weight space vs autograd
-    w = net.color_net[2].weight
-    target = torch.rand_like(out["image"])
-    loss = ((out["image"] - target) ** 2).mean()
-    loss.backward()
+    # the gradients of this branch — every parameter's, against a float64 restatement of the whole step — are held in tests/test_gpu_train_step.py
+    # (chair is this pose at 24 x 24); here only that a backward pass reaches the table
+    ((out["image"] - torch.rand_like(out["image"])) ** 2).mean().backward()
     assert net.encoder.embeddings.grad is not None and net.encoder.embeddings.grad.abs().max() > 0
-    direction = torch.randn_like(w)
-    analytic = float((w.grad * direction).sum())
-    eps = 1e-2
-    vals = []
-    for sgn in (1, -1):
-        with torch.no_grad():
-            w.add_(sgn * eps * direction)
-        vals.append(float(((net.run_cuda(T(o)[None], T(d)[None], perturb=False, T_thresh=1e-2)["image"].detach() - target) ** 2).mean()))
-        with torch.no_grad():
-            w.sub_(sgn * eps * direction)
-    numeric = (vals[0] - vals[1]) / (2 * eps)
-    assert abs(numeric - analytic) < 0.05 * abs(analytic) + 1e-6, (numeric, analytic)
+    assert all(l.weight.grad is not None and l.weight.grad.abs().max() > 0 for l in list(net.sigma_net) + list(net.color_net))
 
 
 def test_update_extra_state_and_mark_untrained_grid():

@@ -262,3 +262,59 @@ def test_sh_dy_dx_and_backward_vs_autograd():
     for deg in (1, 2, 3):
         dd = otr.sh_encode_dy_dx(d, deg)
         assert np.array_equal(dd.reshape(-1, 3, deg * deg), dy_dx.reshape(-1, 3, 16)[:, :, :deg * deg])
+
+
+def test_density_cells_partial_restatement():
+    """oracle.training.density_cells_partial against the reference's tensor expressions (renderer.py:501-516) written out with torch on the CPU, with
+    randint(0, n_occ) replaced by floor(u * n_occ): the occupied list is ascending, j is one float32 multiply truncated and clamped, each cascade
+    jitters by its own half cell, and an empty occupied list gives -1 / zeros."""
+    H, bound = 8, 4.0
+    rng = np.random.default_rng(0)
+    N = 37
+    grid = rng.uniform(-1, 1, H ** 3).astype(np.float32)
+    grid[:3] = (0.0, -0.0, -1.0)
+    coords = rng.integers(0, H, (N, 3)).astype(np.int32)
+    pick = rng.random(N).astype(np.float32)
+    pick[:2] = (0.0, np.nextafter(np.float32(1), np.float32(0)))
+    noise = rng.random((2 * N, 3)).astype(np.float32)
+    occ = torch.nonzero(torch.from_numpy(grid) > 0).squeeze(-1)
+    assert occ[0] >= 3 and bool((occ[1:] > occ[:-1]).all())
+    n_occ = len(occ)
+    pick[2] = np.float32(5 / n_occ)
+    for cas in range(3):
+        idx, xyzs, tmp = otr.density_cells_partial(cas, H, bound, coords, pick, noise, grid)
+        assert idx.dtype == np.int32 and xyzs.dtype == np.float32 and tmp.shape == (H ** 3,) and (tmp == -1).all()
+        j = torch.clamp((torch.from_numpy(pick) * np.float32(n_occ)).to(torch.int64), 0, n_occ - 1)
+        assert j[0] == 0 and j[1] == n_occ - 1 and j[2] in (4, 5)
+        want_idx = torch.cat([torch.from_numpy(oracle.morton3D(coords)).long(), occ[j]])
+        assert np.array_equal(idx, want_idx.numpy())
+        c = torch.from_numpy(np.concatenate([coords, oracle.morton3D_invert(occ[j].numpy().astype(np.int32))]).astype(np.float32))
+        bnd = min(2 ** cas, bound)
+        half = np.float32(bnd / H)
+        want = (2 * c / (H - 1) - 1) * (bnd - half) + (torch.from_numpy(noise) * 2 - 1) * half      # :510-516
+        assert np.array_equal(xyzs, want.numpy())
+        assert np.abs(xyzs).max() <= bnd and np.abs(xyzs - otr._cell_centres(cas, H, bound)[0][idx]).max() <= half
+    idx, xyzs, tmp = otr.density_cells_partial(1, H, bound, coords, pick, noise, np.minimum(grid, 0))
+    assert np.array_equal(idx[:N], oracle.morton3D(coords)) and (idx[N:] == -1).all() and not xyzs[N:].any() and xyzs[:N].any()
+    # float32, not float64: 0.8181818f * 11 is 8.99999976 exactly and rounds to 9.0 in float32, where float64 would truncate to 8
+    u = np.float32(0.8181818)
+    assert int(u * np.float32(11)) == 9 and int(float(u) * 11) == 8
+    g11 = np.zeros(H ** 3, np.float32)
+    g11[10:120:10] = 1
+    assert otr.density_cells_partial(0, H, bound, coords[:1], [u], noise[:2], g11)[0][1] == 100
+
+
+def test_density_scatter_restatement():
+    tmp0 = np.full(16, -1, np.float32)
+    idx = np.array([3, 5, -1, 3, 7, 5, -1, 9], np.int32)
+    sig = np.array([1, 2, 3, 4, 5, 2, 6, 7], np.float32)
+    tmp, ambiguous = otr.density_scatter(idx, sig, tmp0)
+    t = torch.from_numpy(tmp0.copy())
+    live = idx >= 0
+    t[torch.from_numpy(idx[live]).long()] = torch.from_numpy(sig[live])      # tmp_grid[cas, indices] = sigmas (:527)
+    keep = ~ambiguous
+    assert np.array_equal(tmp[keep], t.numpy()[keep]) and (tmp0 == -1).all()
+    assert np.flatnonzero(ambiguous).tolist() == [3] and tmp[3] in (1, 4)    # cell 5 got the same value twice: not ambiguous
+    assert tmp[5] == 2 and tmp[7] == 5 and tmp[9] == 7 and (np.delete(tmp, [3, 5, 7, 9]) == -1).all()
+    tmp, ambiguous = otr.density_scatter(np.zeros(0, np.int32), np.zeros(0, np.float32), tmp0)
+    assert np.array_equal(tmp, tmp0) and not ambiguous.any()
