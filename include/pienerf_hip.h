@@ -682,6 +682,46 @@ int pn_draw_colliders(const void* contact_state, const pn_collider_style* style,
                       float t_max, float bg_scalar, const float* weights_sum, const float* depth_0, float* image, float* coverage_out,
                       float* collider_t_out, void* stream);
 
+/* The same launch with the object's shadow on the colliders (csrc/pn_colliders.hip; NeRFRenderer.set_collider_shadows).  The light is
+ * directional: shadow_ws / shadow_depth_0 [S S] are weights_sum and depth_0 of a render of the object along the parallel rays of
+ * pienerf_amd.colliders.shadow_rays — texel (i, j) at index j S + i, origin c + D L + ((i + 1/2) 2 / S - 1) half U + ((j + 1/2) 2 / S - 1) half V,
+ * direction -L (a unit vector: the render's t is in world units).  L points from the scene towards the light; U, V are orthonormal to it.
+ * Everything is fp32, one rounding per operation, sums left to right.  For a ray whose hit slot is k at t, x = o + t d as pn_draw_colliders
+ * computes it, r = x - c:
+ *     u = U.r, v = V.r, w = L.r, t_r = D - w                                 the receiver's t along its light ray
+ *     fu = (u + half) (S / (2 half)) - 0.5, fv likewise;  i0 = floor(fu), j0 = floor(fv), a_u = fu - i0, a_v = fv - j0
+ *     sum over the texels (i0 + di, j0 + dj), (di, dj) = (0,0), (1,0), (0,1), (1,1), starting from 0: a texel outside [0, S)^2 adds nothing; else with
+ *     s_m = shadow_ws[idx], t_o = shadow_depth_0[idx] / s_m when s_m > 1e-4, else +inf: it adds (w_u w_v) s_m when t_r > t_o + bias, else nothing,
+ *     w_u = 1 - a_u for di = 0 and a_u for di = 1, w_v likewise           (the object's mean depth along the light ray, as the camera-side test)
+ *     occ_map = clamp(sum, 0, 1)
+ *     with spheres != 0, every valid slot k' != k holding a solid sphere (c', R):  oc = x - c', b = oc.L, disc = b b - (oc.oc - R R);  it blocks the
+ *     light iff disc > 0 and -b + sqrt(disc) > 0;  occ_sph = 1 if any blocks, else 0.  Planes and the container cast nothing.
+ *     occ = max(occ_map, occ_sph);  the slot's colour c of pn_draw_colliders becomes c (1 - strength occ), per component;  shadow_out[i] = occ
+ * The composite, coverage_out and collider_t_out are pn_draw_colliders' own, and so is a ray without a hit (shadow_out = 0).  Hence strength = 0, an
+ * all-zero map without sphere casters, and every ray with occ = 0 give pn_draw_colliders' bits.  The maps are read at execution time (a captured
+ * launch follows them); the light is a by-value kernel argument, baked into a captured launch like the style.
+ * Limits: a collider between two parts of the object is judged against the middle of the column; the object receives no shadow from the colliders; a
+ * sphere's own unlit side is not darkened; no penumbra beyond the bilinear footprint and the object's own soft opacity. */
+typedef struct pn_shadow_light {
+    float c[3];            /* the map's centre */
+    float L[3];            /* unit vector from the scene towards the light */
+    float U[3], V[3];      /* orthonormal to L: the map's axes */
+    float half;            /* the map's half-extent in world units, > 0 */
+    float D;               /* distance of the light rays' origins from c along L */
+    int S;                 /* map resolution, 2 .. 4096 */
+    float strength;        /* in [0, 1] */
+    float bias;            /* world units */
+    int spheres;           /* != 0: solid sphere colliders cast analytic shadows */
+} pn_shadow_light;
+/* pn_draw_colliders' arguments and checks, plus: shadow_ws, shadow_depth_0 [S S]; shadow_out [N] or NULL.  PN_ERR_ARG also for S outside 2 .. 4096, a
+ * non-finite light entry, half <= 0, strength outside [0, 1], a NULL map, a map overlapping an output, shadow_out overlapping an input or another
+ * output.  N == 0: success, nothing launched.  One launch, a thread per ray, 256 threads per workgroup; no atomics, no allocation, no host
+ * synchronisation: legal in a stream capture. */
+int pn_draw_colliders_shadowed(const void* contact_state, const pn_collider_style* style, const float* rays_o, const float* rays_d, uint32_t N,
+                               float t_min, float t_max, float bg_scalar, const float* weights_sum, const float* depth_0, float* image,
+                               float* coverage_out, float* collider_t_out, pn_shadow_light light, const float* shadow_ws, const float* shadow_depth_0,
+                               float* shadow_out, void* stream);
+
 /* Arbitrary rest-space points carried by the simulator's GMLS field (csrc/pn_warp_points.hip; simulator/binding.py: PointBinding.warp; INTEGRATION.md
  * "Deforming mesh").  Per point p, in fp64: pos = sum_{i<8} sum_{c<10} Nx[p,i,c] dof[topo[p,i] 10 + c, :], rounded to fp32 once.  With normals_out:
  * F[r][j] = sum_i sum_c dNx[p,i,j,c] dof[topo[p,i] 10 + c, r], n' = n0 (f1 x f2) + n1 (f2 x f0) + n2 (f0 x f1) with f_j = column j of F and

@@ -26,6 +26,12 @@ class ColliderStyle(C.Structure):
     _fields_ = [("rgb", (f32 * 3) * 8), ("checker", f32), ("checker_dim", f32), ("ambient", f32)]
 
 
+class ShadowLight(C.Structure):
+    """pn_shadow_light (include/pienerf_hip.h): a by-value argument of the shadowed collider overlay's launch."""
+    _fields_ = [("c", f32 * 3), ("L", f32 * 3), ("U", f32 * 3), ("V", f32 * 3), ("half", f32), ("D", f32), ("S", i32), ("strength", f32), ("bias", f32),
+                ("spheres", i32)]
+
+
 # name -> (restype, argtypes); every function declared in include/pienerf_hip.h
 SIGNATURES = {
     "pn_version": (C.c_char_p, []),
@@ -132,6 +138,7 @@ SIGNATURES = {
     "pn_sim_contact_set_collider": (i32, [P, i32, i32, P, P]),
     "pn_sim_contact_rhs": (i32, [i32, i32, P, f64, f64, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "pn_draw_colliders": (i32, [P, C.POINTER(ColliderStyle), P, P, u32, f32, f32, f32, P, P, P, P, P, P]),
+    "pn_draw_colliders_shadowed": (i32, [P, C.POINTER(ColliderStyle), P, P, u32, f32, f32, f32, P, P, P, P, P, ShadowLight, P, P, P, P]),
     "pn_sim_warp_points_group": (i32, []),
     "pn_sim_warp_points": (i32, [i32, i32, P, P, P, P, P, P, P, P]),
     "pn_mc_work_bytes": (u64, [i32, i32, i32]),

@@ -2,12 +2,15 @@
 
 ``collider_style`` builds the launch's by-value style; ``draw_colliders_torch`` restates the law in torch ops on the device, the baseline
 tools/time_colliders.py times the HIP launch against (the tests compare the launch with tests/colliders_reference.py's numpy instead).
+
+``shadow_light`` builds the directional light of the shadowed launch (pn_draw_colliders_shadowed) and ``shadow_rays`` the parallel rays its
+opacity map is rendered along (NeRFRenderer.set_collider_shadows).
 """
 import math
 
 import torch
 
-from ._lib import ColliderStyle
+from ._lib import ColliderStyle, ShadowLight
 
 SLOTS = 8
 PLANE, SPHERE, CONTAINER = 1, 2, 3
@@ -36,6 +39,70 @@ def collider_style(rgb=None, types=None, checker=0.0, checker_dim=0.6, ambient=0
     if not 0.0 <= st.ambient <= 1.0:
         raise ValueError(f"collider_style: ambient must be in [0, 1], got {ambient!r}")
     return st
+
+
+def _light_frame(L):
+    """U = normalised L x e, e the coordinate axis on which |L| is smallest (lowest index on ties), V = L x U: the checker's rule, in Python floats."""
+    a = [abs(v) for v in L]
+    if a[0] <= a[1] and a[0] <= a[2]:
+        u = [0.0, L[2], -L[1]]
+    elif a[1] <= a[2]:
+        u = [-L[2], 0.0, L[0]]
+    else:
+        u = [L[1], -L[0], 0.0]
+    n = math.sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2])
+    u = [v / n for v in u]
+    return u, [L[1] * u[2] - L[2] * u[1], L[2] * u[0] - L[0] * u[2], L[0] * u[1] - L[1] * u[0]]
+
+
+def shadow_light(direction=(0.4, 1.0, 0.3), strength=0.6, resolution=256, bound=1.0, min_near=0.2, centre=(0, 0, 0), extent=None, bias=None, spheres=True):
+    """A ShadowLight (pn_shadow_light), built in fp64 and rounded once.  `direction` points from the scene towards the light (any length); the map of
+    `resolution`^2 texels is centred on `centre` and spans +-`extent` (None: sqrt(3) `bound`, which covers the box [-bound, bound]^3 from every direction);
+    the light rays start half + 2 `min_near` from the centre, so each enters the box beyond min_near; `bias` (None: 1.5 texels) keeps a receiver from
+    shadowing itself; `spheres`: solid sphere colliders cast analytic shadows.  ValueError for a zero or non-finite direction, strength outside [0, 1],
+    resolution outside 2 .. 4096, a non-positive extent or a negative bias."""
+    d = [float(v) for v in direction]
+    c = [float(v) for v in centre]
+    n = math.sqrt(sum(v * v for v in d)) if len(d) == 3 and all(math.isfinite(v) for v in d) else 0.0
+    if not (math.isfinite(n) and n > 0.0):
+        raise ValueError(f"shadow_light: direction must be three finite numbers, not all zero, got {direction!r}")
+    if len(c) != 3 or not all(math.isfinite(v) for v in c):
+        raise ValueError(f"shadow_light: centre must be three finite numbers, got {centre!r}")
+    strength = float(strength)
+    if not 0.0 <= strength <= 1.0:
+        raise ValueError(f"shadow_light: strength must be in [0, 1], got {strength!r}")
+    S = int(resolution)
+    if S != resolution or not 2 <= S <= 4096:
+        raise ValueError(f"shadow_light: resolution must be an integer in 2 .. 4096, got {resolution!r}")
+    half = math.sqrt(3.0) * float(bound) if extent is None else float(extent)
+    if not (math.isfinite(half) and half > 0.0):
+        raise ValueError(f"shadow_light: the extent must be a positive finite number, got {half!r}")
+    bias = 1.5 * 2.0 * half / S if bias is None else float(bias)
+    if not (math.isfinite(bias) and bias >= 0.0):
+        raise ValueError(f"shadow_light: bias must be a finite number >= 0, got {bias!r}")
+    min_near = float(min_near)
+    if not math.isfinite(min_near):
+        raise ValueError(f"shadow_light: min_near must be finite, got {min_near!r}")
+    L = [v / n for v in d]
+    U, V = _light_frame(L)
+    lt = ShadowLight()
+    for j in range(3):
+        lt.c[j], lt.L[j], lt.U[j], lt.V[j] = c[j], L[j], U[j], V[j]
+    lt.half, lt.D, lt.S, lt.strength, lt.bias, lt.spheres = half, half + 2.0 * min_near, S, strength, bias, int(bool(spheres))
+    return lt
+
+
+def shadow_rays(light, device):
+    """The light's parallel rays, (rays_o, rays_d) [S^2, 3] fp32 on `device`: texel (i, j) at index j S + i starts at
+    c + D L + ((i + 1/2) 2 / S - 1) half U + ((j + 1/2) 2 / S - 1) half V and runs along -L.  Built in fp64 from the light's fp32 members, rounded once."""
+    S = int(light.S)
+    vec = lambda v: torch.tensor([float(x) for x in v], dtype=torch.float64)   # noqa: E731
+    c, L, U, V = vec(light.c), vec(light.L), vec(light.U), vec(light.V)
+    g = ((torch.arange(S, dtype=torch.float64) + 0.5) * 2.0 / S - 1.0) * float(light.half)
+    o = (c + float(light.D) * L).view(1, 1, 3) + g.view(1, S, 1) * U.view(1, 1, 3) + g.view(S, 1, 1) * V.view(1, 1, 3)   # [j, i, 3]
+    rays_o = o.reshape(S * S, 3).to(torch.float32)
+    rays_d = (-L).to(torch.float32).view(1, 3).expand(S * S, 3)
+    return rays_o.contiguous().to(device), rays_d.contiguous().to(device)
 
 
 def _dot(a, b):

@@ -133,7 +133,7 @@ class SimRenderHarness:
             self._drag_frame = ("eager", out["depth_0"].reshape(H, W), m.p_def, pose, intrinsics)
         res = {"image": out["image"].reshape(-1, H, W, 3), "depth": out["depth"].reshape(-1, H, W), "depth_0": out["depth_0"].reshape(-1, H, W),
                "rays_o": rays["rays_o"], "rays_d": rays["rays_d"]}
-        res.update({k: out[k] for k in ("coverage", "collider_t") if k in out})   # draw_colliders(): the overlay's own outputs
+        res.update({k: out[k] for k in ("coverage", "collider_t", "shadow") if k in out})   # draw_colliders() / cast_shadows(): the overlay's own outputs
         return res
 
     # ------------------------------------------------------------------ whole step as one HIP graph
@@ -156,7 +156,7 @@ class SimRenderHarness:
         # graph's pool and could be handed out again
         res = {"image": out["image"].reshape(-1, H, W, 3), "depth": out["depth"].reshape(-1, H, W), "depth_0": out["depth_0"].reshape(-1, H, W),
                "weights_sum": out["weights_sum"], "rays_o": rays["rays_o"], "rays_d": rays["rays_d"], "_ip": (IP_pos, IP_F, IP_dF)}
-        res.update({k: out[k] for k in ("coverage", "collider_t") if k in out})   # draw_colliders(): render_continue writes them again
+        res.update({k: out[k] for k in ("coverage", "collider_t", "shadow") if k in out})   # draw_colliders() / cast_shadows(): render_continue writes them again
         return res
 
     @torch.no_grad()
@@ -219,8 +219,10 @@ class SimRenderHarness:
         now = self.model.collider_overlay_key()
         if now is not None and captured is None:
             raise RuntimeError(f"colliders: {what} was captured before draw_colliders(), its frames do not draw the colliders: {again} again")
+        if now is not None and captured is not None and len(now) > len(captured):
+            raise RuntimeError(f"colliders: {what} was captured before cast_shadows(), its frames cast no shadows: {again} again")
         if now != captured:
-            raise RuntimeError(f"colliders: the overlay (its state buffer, style or t_max) changed since {what} was captured: {again} again")
+            raise RuntimeError(f"colliders: the overlay (its state buffer, style, t_max or the shadows' light) changed since {what} was captured: {again} again")
 
     def draw_colliders(self, style=None, t_max=None):
         """From the next frame on the renders draw the simulator's colliders (NeRFRenderer.set_collider_overlay on Simulator.collider_state(); DESIGN.md
@@ -244,10 +246,36 @@ class SimRenderHarness:
         self.model.clear_collider_overlay()
         return self
 
+    def cast_shadows(self, direction=(0.4, 1.0, 0.3), strength=0.6, resolution=256, **light_kw):
+        """From the next frame on the object casts a shadow onto the drawn colliders (NeRFRenderer.set_collider_shadows): every frame
+        first renders the object along the light's parallel rays into a `resolution`^2 opacity map, on the render's stream in front of the camera's
+        render.  `light_kw` goes to pienerf_amd.colliders.shadow_light, which takes `bound` and `min_near` from the options.  Call it AFTER
+        draw_colliders() (RuntimeError otherwise) and BEFORE capture(): a graph captured without the shadows, or with another light, is refused.
+        step() and capture() / step_graph() cast them; capture_pipelined() raises while they are set."""
+        from .colliders import shadow_light
+        if self.model.collider_overlay_key() is None:
+            raise RuntimeError("cast_shadows: the shadows fall on the drawn colliders: draw_colliders() first")
+        kw = dict(bound=self.opt["bound"], min_near=self.opt["min_near"])
+        kw.update(light_kw)
+        self.model.set_collider_shadows(shadow_light(direction=direction, strength=strength, resolution=resolution, **kw))
+        return self
+
+    def hide_shadows(self):
+        self.model.clear_collider_shadows()
+        return self
+
+    def _shadows_set(self):
+        return getattr(self.model, "_shadows", None) is not None
+
     def _refuse_overlay_form(self, what):
         if self.model.collider_overlay_key() is not None:
             raise RuntimeError(f"colliders: {what} does not draw the colliders (the other ranks / ray batches would need the collider state sent with "
                                "the DOF snapshot): step(), capture() and the single-process capture_pipelined() do; hide_colliders() first")
+
+    def _refuse_shadows_pipelined(self):
+        if self._shadows_set():
+            raise RuntimeError("shadows: the pipelined form casts no shadows — each lane's workspace would need a shadow workspace and map of its own "
+                               "(the follow-up); step() and capture() / step_graph() do; hide_shadows() first")
 
     @torch.no_grad()
     def step_graph(self, pose=None):
@@ -287,8 +315,12 @@ class SimRenderHarness:
         if getattr(self, "_graph_done", None) is not None:
             self._graph_done.synchronize()  # normally long complete: the host only ever runs one frame ahead
             st = self.model.render_status(synchronize=False)
+            alive = st["alive_at_exit"]
+            if self._shadows_set():   # the shadow pass is in the graph too, on a workspace of its own: render_continue finishes it first, then the frame
+                alive += self.model.render_status(synchronize=False, slot=self.model.SHADOW_SLOT)["alive_at_exit"]
+                self.model.last_stats = st
             self._graph_done = None
-            if st["alive_at_exit"] > 0:
+            if alive > 0:
                 g = self._graph_out
                 with self._amp():
                     self.model.render_continue(0, g["rays_o"], g["rays_d"], g, bg_color=None, **self.render_kwargs())
@@ -335,6 +367,7 @@ class SimRenderHarness:
             self._refuse_overlay_form("the frame-parallel pipeline")
         if (render_kw or {}).get("ray_batch"):
             self._refuse_overlay_form("the staged form")
+        self._refuse_shadows_pipelined()
         o = self.opt
         W, H = W or o["W"], H or o["H"]
         on = bool(frame_parallel) and dist.is_available() and dist.is_initialized()
@@ -380,6 +413,7 @@ class SimRenderHarness:
         self._check_contact_captured(self._pipe_contact, "the pipeline", "capture_pipelined()")
         if not getattr(self, "_pipe_single", True):
             self._refuse_overlay_form("the frame-parallel / staged pipeline")
+        self._refuse_shadows_pipelined()
         self._check_overlay_captured(getattr(self, "_pipe_overlay", None), "the pipeline", "capture_pipelined()")
         out = self._pipe.step(pose)
         self.frame = self._pipe.frame

@@ -5,7 +5,8 @@ deformed point cloud and the per-frame IP state the reference's ``main_render.py
     python -m pienerf_amd.main_render --frames 30 --out output_img/chair [--ply model/chair_0.ply] [--ckpt ws/checkpoints/ngp_ep0300.pth]
            [--W 800 --H 800] [--radius 5 --azimuth 0 --elevation 0 --fovy 50] [--force fx fy fz | --drag X0 Y0 X1 Y1] [--pin_shake AX AY AZ HZ] [--pin_twist NX NY NZ DEG HZ [--pin_centre X Y Z]] [--save_ply] [--save_ip_state]
            [--floor Y] [--collide_sphere CX CY CZ R]... [--collide_inside CX CY CZ R] [--contact_stiffness 0.5 --contact_damping 0.5 --friction 0.5
-           --contact_thickness DX/2] [--unpin] [--draw_colliders [--collider_color R G B]... [--checker S]]
+           --contact_thickness DX/2] [--unpin] [--draw_colliders [--collider_color R G B]... [--checker S]
+           [--shadows [--light X Y Z] [--shadow_strength 0.6] [--shadow_res 256]]]
            [--save_mesh [--mesh_resolution 128] [--mesh_threshold 10] [--mesh_con 0] [--mesh_normals] [--mesh_color]]
 
 Without --ply / --ckpt the synthetic chair of pienerf_amd.scene is used (there are no assets on the GPU box).
@@ -20,6 +21,9 @@ spheres (repeatable), a container sphere the object stays inside; --unpin clears
 --draw_colliders draws those colliders into every frame (SimRenderHarness.draw_colliders): a shaded floor with a checker pattern of
 --checker world units (default 2 sim_dx; 0: none) and shaded spheres, depth-tested against the object; --collider_color (repeatable) colours them in slot order
 (the floor first, then the spheres, then the container).  It composes with --bg_radius, --force, --drag, --pin_*, --save_ply and --save_mesh.
+--shadows lets the object (and the solid spheres) cast a shadow onto the drawn colliders (SimRenderHarness.cast_shadows): a directional
+light from --light (a vector from the scene towards the light, default 0.4 1 0.3), darkening by --shadow_strength at most, through an opacity map of
+--shadow_res texels per side rendered from the light every frame.
 Without --ckpt such a run renders and meshes the SHAPED synthetic checkpoint (its density field has the solid's shape; the plain one's does not).
 Reference: main_gui.py:20-66 (model + simulator construction), nerf/gui.py:556-645 (test_step: IP info -> substep -> render),
 main_render.py:47-104 (frame loop, save_image), simulator/solver.py:109-113 (OutputToPly).
@@ -111,7 +115,19 @@ def configure_overlay(h, args):
     except ValueError as e:
         raise SystemExit(f"--draw_colliders: {e}")
     h.draw_colliders(style)
+    configure_shadows(h, args)
     return style
+
+
+def configure_shadows(h, args):
+    """--shadows / --light / --shadow_strength / --shadow_res as one call on the harness, behind draw_colliders."""
+    if not args.shadows:
+        return
+    d = lambda v, dflt: dflt if v is None else v
+    try:
+        h.cast_shadows(direction=d(args.light, (0.4, 1.0, 0.3)), strength=d(args.shadow_strength, 0.6), resolution=d(args.shadow_res, 256))
+    except ValueError as e:
+        raise SystemExit(f"--shadows: {e}")
 
 
 def check_overlay_args(args):
@@ -120,6 +136,10 @@ def check_overlay_args(args):
         raise SystemExit("--draw_colliders needs --floor, --collide_sphere or --collide_inside")
     if not args.draw_colliders and (args.collider_color or args.checker is not None):
         raise SystemExit("--collider_color / --checker need --draw_colliders")
+    if args.shadows and not args.draw_colliders:
+        raise SystemExit("--shadows needs --draw_colliders")
+    if not args.shadows and (args.light is not None or args.shadow_strength is not None or args.shadow_res is not None):
+        raise SystemExit("--light / --shadow_strength / --shadow_res need --shadows")
 
 
 def run(args):
@@ -234,6 +254,10 @@ def parser():
     ap.add_argument("--collider_color", type=float, nargs=3, action="append", default=None, metavar=("R", "G", "B"),
                     help="a collider's colour, in slot order; repeatable (default: a light grey for a plane, a mid grey otherwise)")
     ap.add_argument("--checker", type=float, default=None, metavar="S", help="cell size of the floor's checker pattern (default: 2 sim_dx; 0: none)")
+    ap.add_argument("--shadows", action="store_true", help="the object casts a shadow onto the drawn colliders (DESIGN.md 4.12); needs --draw_colliders")
+    ap.add_argument("--light", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"), help="a vector from the scene towards the light (default: 0.4 1 0.3)")
+    ap.add_argument("--shadow_strength", type=float, default=None, metavar="F", help="how dark a full shadow is, in [0, 1] (default 0.6)")
+    ap.add_argument("--shadow_res", type=int, default=None, metavar="S", help="texels per side of the light's opacity map, 2 .. 4096 (default 256)")
     ap.add_argument("--save_ply", action="store_true")
     ap.add_argument("--save_ip_state", action="store_true")
     ap.add_argument("--save_mesh", action="store_true", help="write the deforming surface mesh of every frame as OUT/mesh_{f}.ply (rest mesh bound to the simulator, "

@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 
 from .. import raymarching
-from .._lib import ColliderStyle, RenderOpts, check, lib, ptr, require_gpu, stream_ptr
+from .._lib import ColliderStyle, RenderOpts, ShadowLight, check, lib, ptr, require_gpu, stream_ptr
 from .utils import get_pnts_in_grids
 
 
@@ -79,6 +79,7 @@ class NeRFRenderer(nn.Module):
         self._frames = {}
         self.last_stats = None
         self._overlay = None   # set_collider_overlay: (contact state on the device, ColliderStyle, t_max)
+        self._shadows = None   # set_collider_shadows: the light, its rays and the map buffers
 
     def forward(self, x, d):
         raise NotImplementedError()
@@ -126,13 +127,67 @@ class NeRFRenderer(nn.Module):
 
     def clear_collider_overlay(self):
         self._overlay = None
+        self._shadows = None
 
     def collider_overlay_key(self):
-        """What a captured render bakes in of the overlay (None without one): the state's address, the style's bytes, t_max."""
+        """What a captured render bakes in of the overlay (None without one): the state's address, the style's bytes, t_max — and with shadows set the
+        light's bytes and the map buffers' addresses."""
         if self._overlay is None:
             return None
         state, style, t_max = self._overlay
-        return (state.data_ptr(), bytes(style), t_max)
+        key = (state.data_ptr(), bytes(style), t_max)
+        if self._shadows is not None:
+            sh = self._shadows
+            key += (bytes(sh["light"]), sh["shadow_ws"].data_ptr(), sh["shadow_depth_0"].data_ptr())
+        return key
+
+    # ------------------------------------------------------------------ the object's shadow on the drawn colliders (DESIGN.md 4.12)
+    SHADOW_SLOT = 900   # the shadow pass's frame workspace: the pipeline's lanes use 0 .. lanes * depth - 1, the tile-parallel form 800
+
+    def set_collider_shadows(self, light):
+        """From now on the deformed render first renders the object along `light`'s parallel rays (a ShadowLight: pienerf_amd.colliders.shadow_light)
+        into an opacity map — the existing render on the frame workspace SHADOW_SLOT, same IP state, options and async_trips, no overlay and no
+        background — and the overlay's launch looks the map up while it draws (pn_draw_colliders_shadowed; include/pienerf_hip.h has the law).  The
+        renderer owns the light rays and the map buffers `shadow_ws` / `shadow_depth_0` [S^2]; their addresses stay until the next call.  The returned
+        dict gains 'shadow' [N]: the occlusion per camera ray, 0 where no collider is seen.  The light is baked into a captured launch like the style.
+        RuntimeError without a collider overlay."""
+        from ..colliders import shadow_rays
+        if self._overlay is None:
+            raise RuntimeError("set_collider_shadows: the shadows fall on the drawn colliders: set_collider_overlay() first")
+        if not isinstance(light, ShadowLight):
+            raise ValueError("set_collider_shadows: `light` is a ShadowLight (pienerf_amd.colliders.shadow_light)")
+        dev = self._overlay[0].device
+        rays_o, rays_d = shadow_rays(light, dev)
+        n = rays_o.shape[0]
+        buf = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)   # noqa: E731
+        self._shadows = {"light": light, "rays_o": rays_o, "rays_d": rays_d, "shadow_ws": buf(n), "shadow_depth_0": buf(n), "image": buf(n, 3), "depth": buf(n)}
+        return self
+
+    def clear_collider_shadows(self):
+        self._shadows = None
+
+    @property
+    def shadow_ws(self):
+        return self._shadows["shadow_ws"] if self._shadows is not None else None
+
+    @property
+    def shadow_depth_0(self):
+        return self._shadows["shadow_depth_0"] if self._shadows is not None else None
+
+    def _shadow_out(self):
+        sh = self._shadows
+        return {"image": sh["image"], "depth": sh["depth"], "depth_0": sh["shadow_depth_0"], "weights_sum": sh["shadow_ws"]}
+
+    def _render_shadow_map(self, dt_gamma, max_steps, T_thresh, kwargs):
+        """The shadow pass, on the current stream in front of the camera's render.  ray_tile_w is set explicitly: S^2 == W H must not select the image
+        tiling by accident (results do not depend on it).  last_stats stays the main frame's; the pass's own are read with render_status(slot=SHADOW_SLOT)."""
+        sh = self._shadows
+        kw = dict(kwargs, frame_slot=self.SHADOW_SLOT, out_buffers=self._shadow_out(), ray_tile_w=0, _shadow_pass=True)
+        keep = self.last_stats
+        try:
+            self.rund_cuda(sh["rays_o"], sh["rays_d"], dt_gamma=dt_gamma, bg_color=0, perturb=False, max_steps=max_steps, T_thresh=T_thresh, **kw)
+        finally:
+            self.last_stats = keep
 
     def _refuse_overlay(self, what):
         if self._overlay is not None:
@@ -141,11 +196,12 @@ class NeRFRenderer(nn.Module):
 
     def _draw_colliders(self, rays_o, rays_d, bg_scalar, weights_sum, depth_0, image, out, ob=None):
         """Enqueues the overlay's launch on the current stream, in place in `image` (the frame composited over 0); 'coverage' and 'collider_t' of `out`
-        (then of `ob`, else allocated) receive its other outputs.  Returns (coverage, collider_t)."""
+        (then of `ob`, else allocated) receive its other outputs, and with shadows 'shadow'.  Returns [coverage, collider_t] or [coverage, collider_t, shadow]."""
         state, style, t_max = self._overlay
         N = image.shape[0]
         res = []
-        for name in ("coverage", "collider_t"):
+        sh = self._shadows
+        for name in ("coverage", "collider_t") + (("shadow",) if sh is not None else ()):
             t = out.get(name) if out is not None else None
             if t is None and ob is not None:
                 t = ob.get(name)
@@ -153,8 +209,13 @@ class NeRFRenderer(nn.Module):
                 t = torch.empty(N, dtype=torch.float32, device=image.device)
             assert t.shape == (N,) and t.dtype == torch.float32 and t.is_contiguous()
             res.append(t)
-        check(lib().pn_draw_colliders(ptr(state), C.byref(style), ptr(rays_o), ptr(rays_d), N, float(self.min_near), t_max, float(bg_scalar),
-                                      ptr(weights_sum), ptr(depth_0), ptr(image), ptr(res[0]), ptr(res[1]), stream_ptr()), "draw_colliders")
+        if sh is not None:
+            check(lib().pn_draw_colliders_shadowed(ptr(state), C.byref(style), ptr(rays_o), ptr(rays_d), N, float(self.min_near), t_max, float(bg_scalar),
+                                                   ptr(weights_sum), ptr(depth_0), ptr(image), ptr(res[0]), ptr(res[1]), sh["light"], ptr(sh["shadow_ws"]),
+                                                   ptr(sh["shadow_depth_0"]), ptr(res[2]), stream_ptr()), "draw_colliders_shadowed")
+        else:
+            check(lib().pn_draw_colliders(ptr(state), C.byref(style), ptr(rays_o), ptr(rays_d), N, float(self.min_near), t_max, float(bg_scalar),
+                                          ptr(weights_sum), ptr(depth_0), ptr(image), ptr(res[0]), ptr(res[1]), stream_ptr()), "draw_colliders")
         return res
 
     # ------------------------------------------------------------------ entry point (renderer.py:587-599)
@@ -252,7 +313,10 @@ class NeRFRenderer(nn.Module):
         p_def, p_ori, F_IP, dF_IP = self._ip_state(device)
         assert p_def.shape == p_ori.shape and p_ori.shape[0] > 0  # renderer.py:816-817
         n_vtx = p_ori.shape[0]
-        overlay = self._overlay is not None
+        shadow_pass = bool(kwargs.get("_shadow_pass"))   # this call IS the shadow pass: the object alone over 0, no overlay, no background
+        overlay = self._overlay is not None and not shadow_pass
+        if overlay and self._shadows is not None:
+            self._render_shadow_map(dt_gamma, max_steps, T_thresh, kwargs)
         # with an overlay the driver composites over 0 as well: the scalar background goes in behind the colliders, in the overlay's launch
         o = self._deformed_opts(dt_gamma, 0.0 if (bg_tensor is not None or overlay) else bg_color, max_steps, T_thresh, kwargs, n_rays=N)
         ob = kwargs.get("out_buffers")  # extension: caller-owned outputs (the frame pipeline packs image | depth | depth_0 into one buffer -> one D2H)
@@ -282,10 +346,13 @@ class NeRFRenderer(nn.Module):
         res = {"depth": depth.view(*prefix), "depth_0": depth_0.view(*prefix), "weights_sum": weights_sum}
         covered = weights_sum   # what the background is blended with: the object's own opacity, or with an overlay the object's and the colliders'
         if overlay:
-            covered, res["collider_t"] = self._draw_colliders(rays_o, rays_d, 0.0 if (bg_tensor is not None or self.bg_radius > 0) else bg_color,
-                                                              weights_sum, depth_0, image, None, ob)
+            drawn = self._draw_colliders(rays_o, rays_d, 0.0 if (bg_tensor is not None or self.bg_radius > 0) else bg_color, weights_sum, depth_0, image,
+                                         None, ob)
+            covered, res["collider_t"] = drawn[0], drawn[1]
             res["coverage"] = covered
-        if self.bg_radius > 0:
+            if len(drawn) == 3:
+                res["shadow"] = drawn[2]
+        if self.bg_radius > 0 and not shadow_pass:
             self.blend_background(rays_o, rays_d, covered, image)   # in place: `image` may be the caller's out_buffers
         elif bg_tensor is not None:
             image = image + (1 - covered).unsqueeze(-1) * bg_tensor
@@ -302,7 +369,19 @@ class NeRFRenderer(nn.Module):
         N = rays_o.shape[0]
         if self.bg_radius > 0:
             bg_color = 0
-        overlay = self._overlay is not None
+        shadow_pass = bool(kwargs.get("_shadow_pass"))
+        overlay = self._overlay is not None and not shadow_pass
+        if overlay and self._shadows is not None and not static:
+            # a shadow pass that ran out of its fixed trips is finished first, by this same continue on its own slot; the main frame's continue below
+            # then rewrites `image` from the accumulator and applies the overlay again, over the finished map
+            keep = self.last_stats
+            try:
+                if self.SHADOW_SLOT in self._frames and self.render_status(synchronize=True, slot=self.SHADOW_SLOT)["alive_at_exit"] > 0:
+                    sh = self._shadows
+                    self.render_continue(self.SHADOW_SLOT, sh["rays_o"], sh["rays_d"], self._shadow_out(), n_trips=n_trips, dt_gamma=dt_gamma, bg_color=0,
+                                         max_steps=max_steps, T_thresh=T_thresh, **dict(kwargs, ray_tile_w=0, _shadow_pass=True))
+            finally:
+                self.last_stats = keep
         if static:
             self._refuse_overlay("the static render (render_continue with static=True)")
             o = self._static_opts(dt_gamma, 1 if bg_color is None else bg_color, max_steps, T_thresh)
@@ -320,9 +399,12 @@ class NeRFRenderer(nn.Module):
         if overlay:
             if "depth_0" not in out:
                 raise RuntimeError("render_continue: the collider overlay composites against depth_0: pass the dict the deformed render returned")
-            covered, ct = self._draw_colliders(rays_o, rays_d, 0.0 if self.bg_radius > 0 else (1 if bg_color is None else bg_color), ws, depth_0, image, out)
-            out["coverage"], out["collider_t"] = covered, ct
-        if self.bg_radius > 0:
+            drawn = self._draw_colliders(rays_o, rays_d, 0.0 if self.bg_radius > 0 else (1 if bg_color is None else bg_color), ws, depth_0, image, out)
+            covered = drawn[0]
+            out["coverage"], out["collider_t"] = drawn[0], drawn[1]
+            if len(drawn) == 3:
+                out["shadow"] = drawn[2]
+        if self.bg_radius > 0 and not shadow_pass:
             self.blend_background(rays_o, rays_d, covered, image)
         if stats is not None:
             self._set_stats(stats)
