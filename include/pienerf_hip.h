@@ -348,6 +348,15 @@ typedef struct {
                              pre-pass, first trip, simulator) find CUs whose LDS is free: measured on the chair with three render lanes, 64 / 96 / 128 / 160 /
                              192 / 256 workgroups: 1 798 / 1 939 / 1 937 / 1 874 / 1 799 / 1 721 steps/s (profiles/r04_fused_grid_sweep.txt);
                              harness.capture_pipelined passes half the CUs when it runs more than one lane.  The results do not depend on it. */
+    int fused_order;      /* >= 0 (0, the default): a workgroup of the fused launch draws the packets of its share LONGEST FIRST — a packet is 8 consecutive
+                             entries of the alive list, its length the largest far - t of its rays (what the ray still has to march; the frame prologue has
+                             shortened `fars` to where the ray's candidates end), equal lengths in list order (csrc/pn_fused_order.h).  The launch is as
+                             long as its longest wave, and what decides a workgroup's end is the rounds its last rays need one after the other: a long ray
+                             drawn last costs all of them behind everybody else's work.  The shares stay what they are — no ray moves between
+                             workgroups, packets stay packets.  The first 512 packets of a share are ordered, the ones behind them follow in list order.
+                             Acts on the form whose rays come from the alive list (neither fused_whole nor fused_fold took the frame); the other two
+                             draw from lists that fill while the launch runs.  < 0: list order, what the launch did before.  The results do not depend on
+                             it: every ray's march, network tiles and composite are a function of the ray alone. */
 } pn_render_opts;
 int pn_frame_create(pn_frame** out, uint32_t max_rays, uint32_t max_vtx, uint32_t max_grid_cells);
 void pn_frame_destroy(pn_frame* f);
@@ -446,6 +455,9 @@ int pn_frame_march_counters(pn_frame* f, int enable, uint64_t* counters_host, vo
  * of the last render's fused launch (0 later trips only, 1 whole frame, 2 first trip folded in);
  * *first_trip_out (may be NULL) = the trip at which the last render on f switched to the fused launch, -1 if it did not.  reset != 0: zero the sums. */
 int pn_frame_fused_clocks(pn_frame* f, uint64_t* clocks_host, int* first_trip_out, int reset, void* stream);
+/* The drawing order of pn_render_opts.fused_order for ONE share, computed on the host by the functions the kernel runs (csrc/pn_fused_order.h): rays_t /
+ * fars [host, n_rays] are the share's rays in list order, perm_out [host, ceil(n_rays / 8)] receives the packet drawn k-th.  No GPU needed. */
+int pn_fused_order_host(const float* rays_t, const float* fars, int n_rays, int* perm_out);
 /* With bit 1 of `enable` set: the per-trip durations (ms, HIP events on the launch stream) of the last blocking render:
  * *n_trips_out entries in each array. */
 /* Diagnostics: the device's per-trip records of the last render on `f` as int[max_trips][5] = (n_alive, n_step, step_base, n_samples, n_emitted; -1 on trips whose list is compacted)

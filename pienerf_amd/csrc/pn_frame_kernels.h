@@ -182,14 +182,22 @@ __global__ void __launch_bounds__(1024) k_frame_tables(const float* __restrict__
     __shared__ int s_lo[3], s_hi[3];
     if (threadIdx.x < 3) { s_lo[threadIdx.x] = 0x7fffffff; s_hi[threadIdx.x] = -1; }
     __syncthreads();
+    // (in registers and by wave shuffles first, like the bounding box above, then one atomic pair per wave and axis: six atomics per point on three shared
+    // words were ~62 k same-address LDS atomics from this ONE workgroup on every frame's chain)
+    int c_lo[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, c_hi[3] = {-1, -1, -1};
     for (int p = threadIdx.x; p < n_vtx; p += blockDim.x) {
         const int q0 = (int)floorf((p_def[p * 3] - b0) / hgs), q1 = (int)floorf((p_def[p * 3 + 1] - b1) / hgs), q2 = (int)floorf((p_def[p * 3 + 2] - b2) / hgs);
         const int gid = q2 * r1 * r0 + q1 * r0 + q0;
         if (gid < 0 || gid >= n_grid_all) continue;
-        const int c0 = gid % r0, c1 = (gid / r0) % r1, c2 = gid / (r0 * r1);
-        atomicMin(&s_lo[0], c0); atomicMax(&s_hi[0], c0);
-        atomicMin(&s_lo[1], c1); atomicMax(&s_hi[1], c1);
-        atomicMin(&s_lo[2], c2); atomicMax(&s_hi[2], c2);
+        const int cc[3] = {gid % r0, (gid / r0) % r1, gid / (r0 * r1)};
+#pragma unroll
+        for (int c = 0; c < 3; c++) { c_lo[c] = min(c_lo[c], cc[c]); c_hi[c] = max(c_hi[c], cc[c]); }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { c_lo[c] = min(c_lo[c], __shfl_xor(c_lo[c], o)); c_hi[c] = max(c_hi[c], __shfl_xor(c_hi[c], o)); }
+        if (lane == 0) { atomicMin(&s_lo[c], c_lo[c]); atomicMax(&s_hi[c], c_hi[c]); }
     }
     __syncthreads();
     if (threadIdx.x < 3) {

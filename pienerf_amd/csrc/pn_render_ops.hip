@@ -12,6 +12,8 @@
 // The ops the driver shares nothing with are a unit of their own (pn_ray_ops.hip).
 #include <float.h>
 
+#include <vector>
+
 #include "pn_render_records.h"
 #include "pn_cell_hash.h"
 #include "pn_side_tables.h"
@@ -553,6 +555,7 @@ static int enqueue_fused(const RenderCall& c, const FramePlan& pl, int t, int fo
     fa.xyzs = f->xyzs; fa.dirs = f->dirs; fa.deltas = f->deltas; fa.sigmas = f->sigmas; fa.rgbs = f->rgbs;
     fa.ctl = f->fused_ctl; fa.dev = f->dev; fa.tail_diag = f->tail_counts + t;
     fa.clocks = (f->march_counters_on & 4) ? f->fused_clocks : nullptr;
+    fa.order = o->fused_order >= 0 ? 1 : 0;
     if (whole) {
         fa.active = f->active_seg; fa.active_counts = seg_counter(f, SEG_ACTIVE); fa.active_seg_cap = (int)f->seg_cap; fa.t_resume = f->t_resume;
         fa.blist = f->blist; fa.strag = f->strag; fa.blist_cap = f->blist_cap;
@@ -782,6 +785,21 @@ extern "C" int pn_frame_fused_clocks(pn_frame* f, uint64_t* clocks_host, int* fi
     }
     if (first_trip_out) *first_trip_out = f->fused_first;
     if (reset) PN_HIP_CHECK(hipMemsetAsync(f->fused_clocks, 0, 16 * sizeof(unsigned long long), st));
+    return PN_OK;
+}
+
+// The drawing order of one share of the fused launch's plain form, on the host: the functions of pn_fused_order.h as the kernel runs them.  rays_t / fars
+// [n_rays]: the share's rays in list order (packets of PN_ORDER_PACKET consecutive entries); perm_out [ceil(n_rays / PN_ORDER_PACKET)]: the packet drawn k-th.
+extern "C" int pn_fused_order_host(const float* rays_t, const float* fars, int n_rays, int* perm_out) {
+    PN_REQUIRE(n_rays >= 0 && (n_rays == 0 || (rays_t && fars && perm_out)));
+    const int n_packets = (n_rays + PN_ORDER_PACKET - 1) / PN_ORDER_PACKET;
+    const int n_ord = std::min(n_packets, PN_ORDER_CAP);
+    std::vector<float> keys((size_t)n_ord, 0.0f);
+    for (int k = 0; k < n_ord; k++)
+        for (int s = 0; s < PN_ORDER_PACKET && k * PN_ORDER_PACKET + s < n_rays; s++)
+            keys[k] = fmaxf(keys[k], pn_order_key(rays_t[k * PN_ORDER_PACKET + s], fars[k * PN_ORDER_PACKET + s]));
+    for (int k = 0; k < n_ord; k++) perm_out[pn_order_rank(keys.data(), n_ord, k)] = k;
+    for (int k = n_ord; k < n_packets; k++) perm_out[k] = k;
     return PN_OK;
 }
 

@@ -34,6 +34,7 @@
 #include <cstddef>
 
 #include "pn_net_tile.h"
+#include "pn_fused_order.h"
 
 #define PN_FUSED_MAX_TRIPS 128  // fused trips per frame: (max_steps - 1) / 8 for max_steps <= 1024
 // (-DPN_DBG_PHASES=1 timing builds give march_window a phase clock: the fused launch has clocks of its own and hands it a dummy)
@@ -96,6 +97,8 @@ struct FusedArgs {
     int finalize; float bg; const float* nears; const float* fars_full; float* image_out; float* depth_out;
     // FOLD (MODE 2): the first trip's segmented sample list and the march's tail counters
     const int* list_seg; const int* samp_counts; int list_seg_cap; const int* seg_tail; const int* seg_back;
+    // plain form: != 0: a workgroup draws the packets of its share longest first (pn_fused_order.h), 0: in list order
+    int order;
 };
 
 // The launch's own copy of `fa` in the kernarg segment, re-read WHERE it is used.  The kernel's uniform state (three argument structs: ~45 pointers and
@@ -241,6 +244,7 @@ __global__ void __launch_bounds__(PN_FUSED_WAVES * 64, (PN_FUSED_WAVES + 3) / 4)
     __shared__ int s_bres, s_bready, s_bhead, s_sres, s_sready, s_shead, s_pending, s_a1done;  // WHOLE: the workgroup's list of rays going on, its straggler queue, chunks without their A3
     __shared__ int s_pend[PN_FUSED_MAXCHUNKS];  // WHOLE: positions of each chunk still open
     __shared__ int s_pref[PN_SEGS + 1];
+    __shared__ unsigned short s_perm[PN_ORDER_CAP];  // plain form: the order its share's packets are drawn in (pn_fused_order.h); the QUEUED instances never touch it
 
 #if PN_DBG_PHASES
     pnm3::PhaseClock pk_dummy_;
@@ -475,6 +479,31 @@ __global__ void __launch_bounds__(PN_FUSED_WAVES * 64, (PN_FUSED_WAVES + 3) / 4)
         const int n_packets = (A + 7) >> 3;
         const int my_packets = (int)blockIdx.x < n_packets ? (n_packets - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x : 0;
         share = my_packets * 8;
+        // the order the cursor draws them in (pn_fused_order.h): packet k of the share is entries ((k) * gridDim + blockIdx) * 8 .. + 7 of the alive list, its key
+        // the longest far - t of its rays; 8 lanes read a packet's rays, a thread ranks a packet.  The keys are staged where the waves stage their march
+        // (free until the first round, hence the second barrier).  order == 0: the identity, so the hand-out below is ONE code path.
+        const int n_ord = min(my_packets, PN_ORDER_CAP);
+        float* keys = reinterpret_cast<float*>(stage_all);
+        if (fa.order) {
+            for (int k0 = 0; k0 < n_ord; k0 += PN_FUSED_WAVES * 8) {
+                const int k = k0 + (int)(threadIdx.x >> 3);
+                float key = 0.0f;
+                if (k < n_ord) {
+                    const int gpos = (k * (int)gridDim.x + (int)blockIdx.x) * 8 + sub;
+                    if (gpos < A) {
+                        const int idx = fa.alive[gpos];
+                        key = pn_order_key(a.rays_t[idx], a.fars[idx]);
+                    }
+                }
+                key = fmaxf(key, __shfl_xor(key, 1));
+                key = fmaxf(key, __shfl_xor(key, 2));
+                key = fmaxf(key, __shfl_xor(key, 4));
+                if (k < n_ord && sub == 0) keys[k] = key;
+            }
+            __syncthreads();
+        }
+        for (int k = threadIdx.x; k < n_ord; k += PN_FUSED_WAVES * 64) s_perm[fa.order ? pn_order_rank(keys, n_ord, k) : k] = (unsigned short)k;
+        __syncthreads();
     }
 
     if (WHOLE) {
@@ -570,6 +599,7 @@ __global__ void __launch_bounds__(PN_FUSED_WAVES * 64, (PN_FUSED_WAVES + 3) / 4)
     // 3 072 waves drawing from 64 cursors), and — what matters more — an even END: the launch is bound by each CU's gather path, so a last
     // generation of rays spread over all CUs at 60 % load takes 60 % of the time, while the same rays on 60 % of the CUs (a global pool: the waves
     // that find it empty exit) take all of it.  (WHOLE: the workgroup's own list, in the order its first trip left it.)
+    // Inside a share the packets are drawn longest first (s_perm, built above: pn_fused_order.h) — the shares themselves stay what they were.
     bool pool_empty = false;
     int index = -1;  // this group's ray (the same on its 8 lanes), -1: none
     int j = 0;       // trips it has been through in this launch
@@ -592,7 +622,9 @@ __global__ void __launch_bounds__(PN_FUSED_WAVES * 64, (PN_FUSED_WAVES + 3) / 4)
                 base = __builtin_amdgcn_readfirstlane(base);
                 if (!QUEUED) pool_empty = base + need >= share;
                 const int p = base + my_rank;
-                const int gpos = QUEUED ? p : ((p >> 3) * (int)gridDim.x + (int)blockIdx.x) * 8 + (p & 7);
+                int pk = p >> 3;  // plain form: the packet drawn at this position of the share (s_perm: longest first; behind the ordered prefix, list order)
+                if (!QUEUED && pk < min(share >> 3, PN_ORDER_CAP)) pk = (int)s_perm[pk];
+                const int gpos = QUEUED ? p : (pk * (int)gridDim.x + (int)blockIdx.x) * 8 + (p & 7);
                 if (index < 0 && (QUEUED ? my_rank < take : (p < share && gpos < A))) {
                     index = QUEUED ? my_list[gpos] : fa.alive[gpos];
                     j = QUEUED ? 1 : 0;

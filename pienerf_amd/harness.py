@@ -714,7 +714,11 @@ class _HipBackend:
             # launches fewer on a lane's chain.  Where the blocking frame below finds it applicable (at most N / 8 rays with a sample on the first trip)
             # (measured on the chair, alternating runs on one box: three lanes 1 960 against 1 925 steps/s, --steps 20: 1 801 against 1 790; one frame at a
             # time the launch with the first trip's tiles in front of its rounds is longer than what it replaces, 0.884 against 0.859 ms per step)
-            fold = lanes >= 3 and (not kw.get("fused_whole")) and kw["fused_from"] == 1
+            # — that against the launch drawing its rays in list order.  Drawing each workgroup's longest packets first (pn_render_opts.fused_order, the
+            # default) shortens the launch whose rays come from the alive list by 5-6 %, and does nothing for the folded one, whose rays are listed while it
+            # runs: three lanes 1 503-1 508 against 1 483-1 486 steps/s on one box (EXPERIMENTS.md, "After round 6").  So: folded only in list order
+            ordered = kw.get("fused_order") is None or bool(kw.get("fused_order"))
+            fold = lanes >= 3 and (not kw.get("fused_whole")) and kw["fused_from"] == 1 and not ordered
             if fold:
                 h.step(simulate=False, collect_stats=True, W=W, H=H, render_kw=dict(kw, fused_fold=True, async_trips=0))
                 fold = m.fused_clocks(slot=0)["mode"] == 2

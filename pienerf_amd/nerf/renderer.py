@@ -284,6 +284,8 @@ class NeRFRenderer(nn.Module):
         o.fused_grid = int(kwargs.get("fused_grid") or 0)  # extension: workgroups of that launch (pn_render_opts.fused_grid; 0: one per CU)
         o.fused_fold = int(bool(kwargs.get("fused_fold")))  # extension: ... the first trip's network + composite + compaction folded in (pn_render_opts.fused_fold)
         o.fused_whole = int(bool(kwargs.get("fused_whole")))  # extension: ... the frame's first trip included, where it applies (pn_render_opts.fused_whole)
+        fo = kwargs.get("fused_order")
+        o.fused_order = 0 if (fo is None or fo) else -1  # extension: ... a workgroup draws its longest packets first (pn_render_opts.fused_order; False: list order)
         return o
 
     def _static_opts(self, dt_gamma, bg_scalar, max_steps, T_thresh):
