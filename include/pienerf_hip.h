@@ -734,6 +734,70 @@ int pn_draw_colliders_shadowed(const void* contact_state, const pn_collider_styl
                                float* coverage_out, float* collider_t_out, pn_shadow_light light, const float* shadow_ws, const float* shadow_depth_0,
                                float* shadow_out, void* stream);
 
+/* The simulator's integration points and the drag handle drawn into a rendered frame (csrc/pn_points_overlay.hip; NeRFRenderer.set_point_overlay;
+ * DESIGN.md 4.13): the reference's "render IPs" checkbox (nerf/gui.py:533-540, overlay_point_buffer) and the red and blue discs with the line between
+ * them on a dragged point (gui.py:561-569).  TWO launches on `stream` with the per-frame key buffer `keys` between them, behind the frame driver, the
+ * colliders' launch and the background's blend: they paint onto the finished picture.  pos, F, values, pose16 and drag are DEVICE memory read at
+ * execution time: a captured pair follows the simulator, the camera and the cursor without a recapture.  Everything is fp32, one rounding per
+ * operation, sums left to right.  pose16 is the c2w matrix, row-major: R[r][k] = pose16[4 r + k], c = (pose16[3], pose16[7], pose16[11]).
+ * Projection of a world point x (the camera looks along +z, as gui.py:660-667 and get_rays have it):
+ *     d = x - c;  xc = R[0][0] d0 + R[1][0] d1 + R[2][0] d2, yc and zc likewise with columns 1 and 2 (xc = R^T d);  t = sqrt(d0 d0 + d1 d1 + d2 d2)
+ *     u = xc / zc fx + cx,  v = yc / zc fy + cy      (divide, multiply, add);  drawable iff x, t, u, v are finite and zc > 0
+ * Splat, a thread per point i, 256 per workgroup: a point that is not drawable or has t <= t_min is dropped.  px = floor(u), py = floor(v): row py,
+ * column px, index py W + px.  Every pixel (px + dx, py + dy) inside the image with dx dx + dy dy <= radius^2 (integers) takes an unsigned 64-bit
+ * atomic min of (bits(t) << 32) | i into keys — t > 0, so its bits order as the floats do: per pixel the nearest point wins, the lowest index on
+ * ties, in whatever order the hardware ran anything.  No other atomics.  (A plain load skips the atomic where the stored key is already smaller: min is
+ * monotone, the result cannot change.)
+ * Two deviations from the reference, both its defects: it projects a point BEHIND the camera mirrored through the centre onto the picture (zc < 0 is not
+ * tested), here the point is dropped; and its int() truncates toward zero where this floors, which differs only for u or v in (-1, 0), where the
+ * reference paints an off-screen point onto the border row or column.  Its double swap at gui.py:536-539 amounts to row py, column px.
+ * Resolve, a thread per pixel p: reads keys[p] and, unless it is the empty value ~0, writes ~0 back — the buffer is all-empty between calls (fill it
+ * once when it is allocated).  With a key, i = its low word, t = the float of its high word, s = weights_sum[p]:
+ *     t_obj = depth_0[p] / s when s > 1e-4, else +inf;  t_front = min(t_obj, collider_t[p]) with collider_t, else t_obj      (the colliders' own test)
+ *     visible iff xray != 0 or t <= t_front + bias;  a = alpha when visible, else alpha hidden_alpha;  hidden and hidden_alpha == 0: nothing is drawn
+ *     colour c:  PN_POINT_FLAT: rgb.   Otherwise a scalar v of point i, F = F[i] row-major (F[r][k] = F[9 i + 3 r + k]):
+ *         PN_POINT_STRAIN: C[a][b] = F[0][a] F[0][b] + F[1][a] F[1][b] + F[2][a] F[2][b], E[a][b] = 0.5 (C[a][b] - (a == b)),
+ *                          v = sqrt(sum of E[a][b] E[a][b] over a, then b, starting from 0)                                    (|| 1/2 (F^T F - I) ||_F)
+ *         PN_POINT_VOLUME: v = (F00 (F11 F22 - F12 F21) - F01 (F10 F22 - F12 F20) + F02 (F10 F21 - F11 F20)) - 1                (det F - 1)
+ *         PN_POINT_VALUES: v = values[i]
+ *         u = min(max((v - lo) / (hi - lo), 0), 1);  u < 0.5: w = 2 u, c = ramp[0] + w (ramp[1] - ramp[0]);  else w = 2 (u - 0.5),
+ *         c = ramp[1] + w (ramp[2] - ramp[1]), per component
+ *     image[p] = a c + (1 - a) image[p];  point_id_out[p] = i, point_t_out[p] = t       (else -1 and +inf)
+ * Markers, with drag != NULL and drag->active != 0, in the same launch, per pixel centre q = (column + 1/2, row + 1/2), after the point, in the
+ * reference's order: A = (u, v) of pos[drag->vid] (0 <= vid < n), B = (u, v) of drag->target rounded to fp32 once; an end that is not drawable drops
+ * its disc and the line.  |q - A|^2 <= marker_radius^2: image[p] = (1, 0, 0);  then |q - B|^2 <= marker_radius^2: image[p] = (0, 0, 1);  then with
+ * e = B - A, g = q - A, h = min(max((g.e) / (e.e), 0), 1) (0 when e.e == 0), f = g - h e:  f.f <= (0.5 marker_thickness)^2: image[p] = (1 - 100 / 255) image[p]
+ * (black at alpha 100 / 255).  Squared lengths are x x + y y.  Markers ignore the depth test and t_min and do not write point_id_out.
+ * A pixel with no key and no marker keeps its image bits.  weights_sum, depth_0 and collider_t are only read.
+ * Limits: one point per pixel (the nearest; no blending of several), no anti-aliasing, and a depth test against the object's MEAN depth depth_0 / s: a
+ * point inside a semi-transparent part is wholly in front of it or wholly behind. */
+enum { PN_POINT_FLAT = 0, PN_POINT_STRAIN = 1, PN_POINT_VOLUME = 2, PN_POINT_VALUES = 3 };
+typedef struct pn_point_style {
+    int radius;              /* footprint radius in pixels, 0 .. 8 */
+    int mode;                /* PN_POINT_* */
+    int xray;                /* != 0: every point is visible (the reference's behaviour); 0: depth-tested ("occluded") */
+    float rgb[3];            /* PN_POINT_FLAT's colour */
+    float ramp[3][3];        /* the ramp modes' colours at u = 0, 1/2, 1 */
+    float lo;                /* the ramp's range: u = 0 at lo ... */
+    float hi;                /* ... and 1 at hi */
+    float alpha;             /* in [0, 1] */
+    float hidden_alpha;      /* in [0, 1]: factor on alpha for a point behind the object or a collider; 0: not drawn */
+    float bias;              /* depth-test slack, in units of t */
+    float marker_radius;     /* the drag handle's discs, in pixels (the reference: 10) */
+    float marker_thickness;  /* ... and its line (the reference: 5) */
+} pn_point_style;
+uint64_t pn_points_keys_bytes(int W, int H);   /* 8 W H; 0 for W or H <= 0 */
+/* pos [n,3]; F [n,9] or NULL; values [n] or NULL; pose16 [16] device; intr4_host = (fx, fy, cx, cy) on the HOST, baked into the launch like the style;
+ * weights_sum, depth_0 [W H]; collider_t [W H] or NULL (pn_draw_colliders' collider_t_out); drag: a device pn_drag_state or NULL; keys [W H] uint64,
+ * all ~0 on entry and on exit; image [W H,3] in place; point_id_out [W H] int32 and point_t_out [W H] or NULL.  PN_ERR_ARG for a NULL required
+ * pointer, an output (image, keys, point_id_out, point_t_out) overlapping an input or another output, radius outside 0 .. 8, an unknown mode, a
+ * non-finite style entry, intrinsic or t_min, alpha or hidden_alpha outside [0, 1], hi <= lo in a ramp mode, PN_POINT_STRAIN / PN_POINT_VOLUME
+ * without F, PN_POINT_VALUES without values, n < 0, n or W H beyond int32, W or H <= 0.  n == 0 without a drag: success, nothing launched (with a
+ * drag: the resolve launch alone).  No allocation, no host synchronisation: legal in a stream capture. */
+int pn_draw_points(const float* pos, const float* F, const float* values, int64_t n, const float* pose16, const float* intr4_host, int W, int H,
+                   float t_min, const float* weights_sum, const float* depth_0, const float* collider_t, const void* drag, uint64_t* keys,
+                   pn_point_style style, float* image, int* point_id_out, float* point_t_out, void* stream);
+
 /* Arbitrary rest-space points carried by the simulator's GMLS field (csrc/pn_warp_points.hip; simulator/binding.py: PointBinding.warp; INTEGRATION.md
  * "Deforming mesh").  Per point p, in fp64: pos = sum_{i<8} sum_{c<10} Nx[p,i,c] dof[topo[p,i] 10 + c, :], rounded to fp32 once.  With normals_out:
  * F[r][j] = sum_i sum_c dNx[p,i,j,c] dof[topo[p,i] 10 + c, r], n' = n0 (f1 x f2) + n1 (f2 x f0) + n2 (f0 x f1) with f_j = column j of F and

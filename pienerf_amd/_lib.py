@@ -32,6 +32,12 @@ class ShadowLight(C.Structure):
                 ("spheres", i32)]
 
 
+class PointStyle(C.Structure):
+    """pn_point_style (include/pienerf_hip.h): a by-value argument of the point overlay's launch pair."""
+    _fields_ = [("radius", i32), ("mode", i32), ("xray", i32), ("rgb", f32 * 3), ("ramp", (f32 * 3) * 3), ("lo", f32), ("hi", f32), ("alpha", f32),
+                ("hidden_alpha", f32), ("bias", f32), ("marker_radius", f32), ("marker_thickness", f32)]
+
+
 # name -> (restype, argtypes); every function declared in include/pienerf_hip.h
 SIGNATURES = {
     "pn_version": (C.c_char_p, []),
@@ -140,6 +146,8 @@ SIGNATURES = {
     "pn_sim_contact_rhs": (i32, [i32, i32, P, f64, f64, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "pn_draw_colliders": (i32, [P, C.POINTER(ColliderStyle), P, P, u32, f32, f32, f32, P, P, P, P, P, P]),
     "pn_draw_colliders_shadowed": (i32, [P, C.POINTER(ColliderStyle), P, P, u32, f32, f32, f32, P, P, P, P, P, ShadowLight, P, P, P, P]),
+    "pn_points_keys_bytes": (u64, [i32, i32]),
+    "pn_draw_points": (i32, [P, P, P, C.c_int64, P, P, i32, i32, f32, P, P, P, P, P, PointStyle, P, P, P, P]),
     "pn_sim_warp_points_group": (i32, []),
     "pn_sim_warp_points": (i32, [i32, i32, P, P, P, P, P, P, P, P]),
     "pn_mc_work_bytes": (u64, [i32, i32, i32]),

@@ -51,6 +51,9 @@ UNITS = {
     # the colliders drawn into a frame: per-ray fp32 with decisions in it (hit / miss, checker parity, in front of / behind the object), one rounding per
     # operation in source order, which tests/colliders_reference.py restates in numpy; a ray without a hit gets the frame epilogue's two roundings
     "pn_colliders.hip": ["-ffp-contract=off"],
+    # the integration points and the drag handle drawn into a frame: per-point and per-pixel fp32 with decisions in it (the pixel a point falls on, in
+    # front of / behind the object, inside a disc), one rounding per operation in source order, which tests/points_overlay_reference.py restates in numpy
+    "pn_points_overlay.hip": ["-ffp-contract=off"],
     "pn_warp_points.hip": ["-ffp-contract=fast"],   # bound points warped by the GMLS field: pn_sim_ip.h's accumulation, contracted as in pn_sim.hip
     "pn_mesh.hip": ["-ffp-contract=off"],  # marching cubes: the vertex formula rounds as written (tests/mc_reference.py restates it bit for bit)
     # training batches: the pixel index restates separate torch ops (one rounding each), the keys of the weighted sampler are IEEE quotients, and a

@@ -124,6 +124,8 @@ class SimRenderHarness:
         kw = self.render_kwargs()
         kw.update(render_kw or {})
         kw["collect_stats"] = collect_stats
+        if m.point_overlay_key() is not None:
+            kw["point_pose"] = self._pose_dev[1]   # draw_points(): the camera this frame's rays come from
         with self._amp():
             if fused:
                 out = m.render_deformed(rays["rays_o"], rays["rays_d"], staged=True, bg_color=None, perturb=False, **kw)
@@ -134,6 +136,9 @@ class SimRenderHarness:
         res = {"image": out["image"].reshape(-1, H, W, 3), "depth": out["depth"].reshape(-1, H, W), "depth_0": out["depth_0"].reshape(-1, H, W),
                "rays_o": rays["rays_o"], "rays_d": rays["rays_d"]}
         res.update({k: out[k] for k in ("coverage", "collider_t", "shadow") if k in out})   # draw_colliders() / cast_shadows(): the overlay's own outputs
+        if "point_id" in out:   # draw_points(): the drawn point per pixel, what pick_drawn() reads
+            res.update(point_id=out["point_id"].reshape(-1, H, W), point_t=out["point_t"].reshape(-1, H, W))
+            self._points_frame = (res["point_id"], m.p_def)
         return res
 
     # ------------------------------------------------------------------ whole step as one HIP graph
@@ -149,6 +154,8 @@ class SimRenderHarness:
             self.sim.stepforward()
         kw = self.render_kwargs()
         kw["async_trips"] = n_trips
+        if m.point_overlay_key() is not None:
+            kw["point_pose"] = self._graph_pose
         with self._amp():
             out = m.render_deformed(rays["rays_o"], rays["rays_d"], staged=True, bg_color=None, perturb=False, **kw)
         main.wait_stream(self._sim_stream)
@@ -157,6 +164,7 @@ class SimRenderHarness:
         res = {"image": out["image"].reshape(-1, H, W, 3), "depth": out["depth"].reshape(-1, H, W), "depth_0": out["depth_0"].reshape(-1, H, W),
                "weights_sum": out["weights_sum"], "rays_o": rays["rays_o"], "rays_d": rays["rays_d"], "_ip": (IP_pos, IP_F, IP_dF)}
         res.update({k: out[k] for k in ("coverage", "collider_t", "shadow") if k in out})   # draw_colliders() / cast_shadows(): render_continue writes them again
+        res.update({k: out[k] for k in ("point_id", "point_t") if k in out})   # draw_points(): flat [N], render_continue writes them again
         return res
 
     @torch.no_grad()
@@ -190,6 +198,7 @@ class SimRenderHarness:
         self._graph_pins = self.sim.pin_enabled    # ... and so is its k_pin_rhs launch (Simulator.enable_pin_motion)
         self._graph_contact = self.sim.contact_enabled   # ... and its contact launches (Simulator.enable_contact)
         self._graph_overlay = self.model.collider_overlay_key()   # ... and the render's collider overlay, with its style (draw_colliders)
+        self._graph_points = self.model.point_overlay_key()   # ... and the point overlay's launch pair (draw_points)
         self._graph_form_epoch = self._net_form_epoch()
         return self
 
@@ -224,6 +233,64 @@ class SimRenderHarness:
         if now != captured:
             raise RuntimeError(f"colliders: the overlay (its state buffer, style, t_max or the shadows' light) changed since {what} was captured: {again} again")
 
+    def _check_points_captured(self, captured, what, again):
+        """Positions, pose and drag state are device memory and are followed without a recapture; the launch pair, its style and the intrinsics are in
+        the graph."""
+        now = self.model.point_overlay_key()
+        if now is not None and captured is None:
+            raise RuntimeError(f"points: {what} was captured before draw_points(), its frames do not draw the points: {again} again")
+        if now != captured:
+            raise RuntimeError(f"points: the point overlay (its style, intrinsics, values or drag state) changed since {what} was captured: {again} again")
+
+    def draw_points(self, style=None, markers=True):
+        """From the next frame on the renders draw the simulator's integration points into the finished picture — the reference's "render IPs"
+        checkbox (gui.py:533-540) — and, with `markers`, the drag handle on a dragged point (gui.py:561-569): NeRFRenderer.set_point_overlay with this
+        harness's intrinsics and frame size; DESIGN.md 4.13.  `style`: a PointStyle (None: pienerf_amd.points_overlay.point_style's defaults).  The
+        handle reads the simulator's drag state, so enable_drag() comes first.  Call it BEFORE capture() / capture_pipelined(): a graph captured
+        without the launch pair is refused.  step, capture / step_graph and the single-process capture_pipelined draw the points, every frame those
+        of the state it was rendered from; the frame-parallel, tile-parallel and staged forms raise while it is set.  The returned frames gain
+        'point_id' and 'point_t'."""
+        o = self.opt
+        drag = self.sim._drag if (markers and self.sim.drag_enabled) else None
+        self.model.set_point_overlay(None, self.intrinsics, o["W"], o["H"], style, drag_state=drag)
+        return self
+
+    def hide_points(self):
+        self.model.clear_point_overlay()
+        self._points_frame = None
+        return self
+
+    def _refuse_points_form(self, what):
+        if self.model.point_overlay_key() is not None:
+            raise RuntimeError(f"points: {what} does not draw the points (the other ranks / ray batches hold only a part of the frame the launch pair "
+                               "paints onto): step(), capture() and the single-process capture_pipelined() do; hide_points() first")
+
+    def pick_drawn(self, x, y, point_id=None, ip_pos=None):
+        """An exact pick through the picture: the integration point drawn at pixel (x, y) of the last frame (column x, row y) — that one value of the
+        frame's 'point_id' is read back, no search for the point nearest to an unprojected cursor — is held by the drag (Simulator.drag_hold) with its
+        own position as the target; move() then pulls it.  Returns its index, or -1 where no point was drawn (the drag is left as it was).  The
+        pipelined form passes the retired frame's `point_id` and the positions `ip_pos` it was rendered from."""
+        if not self.sim.drag_enabled:
+            raise RuntimeError("pick_drawn: call enable_drag() first (before capture() / capture_pipelined())")
+        if point_id is None:
+            fr = getattr(self, "_points_frame", None)
+            if fr is None:
+                raise RuntimeError("pick_drawn: no frame with the points drawn has been rendered yet (draw_points(), then a step)")
+            if getattr(self, "_drag_frame", ("",))[0] == "graph":
+                self._check_previous_graph_frame()
+            point_id, ip_pos = fr[0], (fr[1] if ip_pos is None else ip_pos)
+        if ip_pos is None:
+            raise ValueError("pick_drawn: pass ip_pos, the integration-point positions the frame was rendered from")
+        W, H = self.opt["W"], self.opt["H"]
+        x, y = int(x), int(y)
+        if not (0 <= x < W and 0 <= y < H):
+            raise ValueError(f"pick_drawn: pixel ({x}, {y}) is outside the {W} x {H} frame")
+        vid = int(point_id.reshape(-1)[y * W + x].item())
+        if vid < 0:
+            return -1
+        self.sim.drag_hold(vid, ip_pos[vid].detach().cpu().numpy().astype(np.float64))
+        return vid
+
     def draw_colliders(self, style=None, t_max=None):
         """From the next frame on the renders draw the simulator's colliders (NeRFRenderer.set_collider_overlay on Simulator.collider_state(); DESIGN.md
         4.11).  `style`: a ColliderStyle (None: pienerf_amd.colliders.collider_style for the colliders present now, no checker).  Call it BEFORE
@@ -238,8 +305,8 @@ class SimRenderHarness:
     def _order_overlay_behind_setters(self):
         """set_collider's one-thread launch runs on the simulator's force stream; a frame that draws the colliders reads the state on the render's
         stream, so with an overlay that stream first waits for what the force stream holds.  Nothing is enqueued without an overlay."""
-        fs = self.sim.force_stream
-        if self.model.collider_overlay_key() is not None and fs is not None:
+        fs = self.sim.force_stream   # ... and the drag handle of draw_points() reads the drag state, written on the same stream
+        if (self.model.collider_overlay_key() is not None or self.model.point_overlay_reads_drag()) and fs is not None:
             torch.cuda.current_stream(self.device).wait_stream(fs)
 
     def hide_colliders(self):
@@ -287,6 +354,7 @@ class SimRenderHarness:
         self._check_pins_captured(self._graph_pins, "the step graph", "capture()")
         self._check_contact_captured(self._graph_contact, "the step graph", "capture()")
         self._check_overlay_captured(self._graph_overlay, "the step graph", "capture()")
+        self._check_points_captured(getattr(self, "_graph_points", None), "the step graph", "capture()")
         self._check_previous_graph_frame()
         if pose is not None:
             self._graph_pose.copy_(torch.from_numpy(np.asarray(pose, np.float32)).unsqueeze(0))
@@ -302,6 +370,8 @@ class SimRenderHarness:
             self._drag_frame = ("graph", g["depth_0"][0], g["_ip"][0], self._graph_pose_host, self.intrinsics)
         else:
             self._drag_frame = ("graph",)
+        if "point_id" in self._graph_out:
+            self._points_frame = (self._graph_out["point_id"], self._graph_out["_ip"][0])
         return self._graph_out
 
     def finish_graph_frame(self):
@@ -322,8 +392,10 @@ class SimRenderHarness:
             self._graph_done = None
             if alive > 0:
                 g = self._graph_out
+                if self.model.point_overlay_key() is not None:
+                    self.model.p_def, self.model.IP_F, self.model.IP_dF = g["_ip"]   # the point overlay paints the state this frame was rendered from
                 with self._amp():
-                    self.model.render_continue(0, g["rays_o"], g["rays_d"], g, bg_color=None, **self.render_kwargs())
+                    self.model.render_continue(0, g["rays_o"], g["rays_d"], g, bg_color=None, **dict(self.render_kwargs(), point_pose=self._graph_pose))
                 self.graph_continued = getattr(self, "graph_continued", 0) + 1
 
     # ------------------------------------------------------------------ several frames in flight (one GPU, or frame-parallel over a node)
@@ -365,8 +437,10 @@ class SimRenderHarness:
         from .frames import FramePipeline
         if frame_parallel:
             self._refuse_overlay_form("the frame-parallel pipeline")
+            self._refuse_points_form("the frame-parallel pipeline")
         if (render_kw or {}).get("ray_batch"):
             self._refuse_overlay_form("the staged form")
+            self._refuse_points_form("the staged form")
         self._refuse_shadows_pipelined()
         o = self.opt
         W, H = W or o["W"], H or o["H"]
@@ -395,6 +469,7 @@ class SimRenderHarness:
         self._pipe_pins = self.sim.pin_enabled
         self._pipe_contact = self.sim.contact_enabled
         self._pipe_overlay = self.model.collider_overlay_key()
+        self._pipe_points = self.model.point_overlay_key()
         self._pipe_single = not frame_parallel and not (render_kw or {}).get("ray_batch")
         self._drag_frame = ("pipelined",)
         self._pipe_backend = be
@@ -413,8 +488,10 @@ class SimRenderHarness:
         self._check_contact_captured(self._pipe_contact, "the pipeline", "capture_pipelined()")
         if not getattr(self, "_pipe_single", True):
             self._refuse_overlay_form("the frame-parallel / staged pipeline")
+            self._refuse_points_form("the frame-parallel / staged pipeline")
         self._refuse_shadows_pipelined()
         self._check_overlay_captured(getattr(self, "_pipe_overlay", None), "the pipeline", "capture_pipelined()")
+        self._check_points_captured(getattr(self, "_pipe_points", None), "the pipeline", "capture_pipelined()")
         out = self._pipe.step(pose)
         self.frame = self._pipe.frame
         return out
@@ -462,6 +539,8 @@ class SimRenderHarness:
             kw.pop("ray_batch", None)
             if be.kw.get("ray_batch"):
                 kw["ray_batch"] = be.kw["ray_batch"]   # batches keep their own trip schedules: part of what the frame IS, not of how it is launched
+            if m.point_overlay_key() is not None:
+                kw["point_pose"] = be.pose_dev[ws]
             with self._amp():
                 out = m.render_deformed(rays["rays_o"], rays["rays_d"], staged=True, bg_color=None, perturb=False, **kw)
             torch.cuda.synchronize(self.device)
@@ -491,6 +570,7 @@ class SimRenderHarness:
         capped by the time-sequential simulator, this divides the render LATENCY of a frame by the rank count.  Launches are eager."""
         from .frames import TileParallel
         self._refuse_overlay_form("the tile-parallel form")
+        self._refuse_points_form("the tile-parallel form")
         o, m, dev = self.opt, self.model, self.device
         W, H = W or o["W"], H or o["H"]
         ip = tuple(torch.empty((self.sim.n_IP, c), dtype=torch.float32, device=dev) for c in (3, 9, 27))
@@ -517,6 +597,7 @@ class SimRenderHarness:
     def step_tile_parallel(self, pose=None):
         """One sim+render step; every rank gets the full frame: {'image' [1,H,W,3], 'depth' [1,H,W], 'depth_0' [1,H,W]} on the device."""
         self._refuse_overlay_form("the tile-parallel form")
+        self._refuse_points_form("the tile-parallel form")
         if pose is not None:
             self._tile_pose.copy_(torch.from_numpy(np.asarray(pose, np.float32)).view(1, 4, 4).to(self.device))
         full = self._tile.step()
@@ -746,7 +827,7 @@ class _HipBackend:
                     m.p_def, m.IP_F, m.IP_dF = self.ip[ws]
                     rays = get_rays(self.pose_dev[ws], h.intrinsics, H, W, -1)
                     with h._amp():
-                        m.render_deformed(rays["rays_o"], rays["rays_d"], staged=True, bg_color=None, perturb=False, **dict(kw, frame_slot=ws))
+                        m.render_deformed(rays["rays_o"], rays["rays_d"], staged=True, bg_color=None, perturb=False, **self._ws_kw(ws))
             torch.cuda.synchronize(dev)
             if ws == 0 and kw.get("march_throughput") and "march_throughput_trips" not in kw:
                 # the throughput form for every leading trip that still has rays enough to fill the GPU with ONE lane per ray (the trex option set's
@@ -780,7 +861,7 @@ class _HipBackend:
             with _capture(g, stream=s):
                 rays = get_rays(self.pose_dev[ws], h.intrinsics, H, W, -1)
                 with h._amp():
-                    out = m.render_deformed(rays["rays_o"], rays["rays_d"], staged=True, bg_color=None, perturb=False, out_buffers=ob, **dict(kw, frame_slot=ws))
+                    out = m.render_deformed(rays["rays_o"], rays["rays_d"], staged=True, bg_color=None, perturb=False, out_buffers=ob, **self._ws_kw(ws))
             self.graph.append(g)
             # every tensor the graphs touch stays referenced: a tensor freed after capture goes back to the graph's memory pool
             self.rays.append(rays)
@@ -807,6 +888,13 @@ class _HipBackend:
         sim._pin_clock_restore(keep[2])   # ... the pin motion's substep clock
         sim.reset_warm_start()      # ... and its SVD warm start: a replay from here has the bits of a simulator that never warmed up
         torch.cuda.synchronize(dev)
+
+    def _ws_kw(self, ws):
+        """The render options of workspace `ws`: its frame workspace and, with draw_points(), its own camera for the point overlay."""
+        kw = dict(self.kw, frame_slot=ws)
+        if self.h.model.point_overlay_key() is not None:
+            kw["point_pose"] = self.pose_dev[ws]
+        return kw
 
     # ---- streams / events
     def stream(self, name):
@@ -905,7 +993,11 @@ class _HipBackend:
         s = self._streams[f"lane{ws // self.depth}"]
         with torch.cuda.stream(s):
             with h._amp():
-                m.render_continue(ws, self.rays[ws]["rays_o"], self.rays[ws]["rays_d"], self.out[ws], bg_color=None, **self.kw)
+                kw = self._ws_kw(ws)
+                kw.pop("frame_slot")
+                if "point_pose" in kw:
+                    m.p_def, m.IP_F, m.IP_dF = self.ip[ws]   # the point overlay paints the state this frame was rendered from
+                m.render_continue(ws, self.rays[ws]["rays_o"], self.rays[ws]["rays_d"], self.out[ws], bg_color=None, **kw)
             if self.host[ws] is not None:
                 self.copy_out(_HipStream(s), ws, same_buffer=True)
         s.synchronize()
@@ -921,6 +1013,8 @@ class _HipBackend:
         o = self.out[ws]
         H, W, N = self.H, self.W, self.H * self.W
         dev = {"image": o["image"].view(-1, H, W, 3), "depth": o["depth"].view(-1, H, W), "depth_0": o["depth_0"].view(-1, H, W)}
+        if "point_id" in o:   # draw_points(): on the device only (pick_drawn reads one value)
+            dev.update(point_id=o["point_id"].view(-1, H, W), point_t=o["point_t"].view(-1, H, W), ip_pos=self.ip[ws][0])
         if self.host[ws] is None:
             return {"device": dev}
         hb = self.host[ws][self.host_gen[ws]].numpy()

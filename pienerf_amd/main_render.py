@@ -7,6 +7,8 @@ deformed point cloud and the per-frame IP state the reference's ``main_render.py
            [--floor Y] [--collide_sphere CX CY CZ R]... [--collide_inside CX CY CZ R] [--contact_stiffness 0.5 --contact_damping 0.5 --friction 0.5
            --contact_thickness DX/2] [--unpin] [--draw_colliders [--collider_color R G B]... [--checker S]
            [--shadows [--light X Y Z] [--shadow_strength 0.6] [--shadow_res 256]]]
+           [--draw_points [--point_radius 1] [--point_color R G B] [--point_mode flat|strain|volume] [--point_range LO HI] [--point_xray]
+           [--point_alpha 1] [--point_hidden_alpha 0] [--no_drag_marker]]
            [--save_mesh [--mesh_resolution 128] [--mesh_threshold 10] [--mesh_con 0] [--mesh_normals] [--mesh_color]]
 
 Without --ply / --ckpt the synthetic chair of pienerf_amd.scene is used (there are no assets on the GPU box).
@@ -24,6 +26,11 @@ spheres (repeatable), a container sphere the object stays inside; --unpin clears
 --shadows lets the object (and the solid spheres) cast a shadow onto the drawn colliders (SimRenderHarness.cast_shadows): a directional
 light from --light (a vector from the scene towards the light, default 0.4 1 0.3), darkening by --shadow_strength at most, through an opacity map of
 --shadow_res texels per side rendered from the light every frame.
+--draw_points paints the simulator's integration points into every frame (SimRenderHarness.draw_points), the reference's "render IPs"
+checkbox: discs of --point_radius pixels in --point_color, or coloured by --point_mode strain (|1/2 (F^T F - I)|) or volume (det F - 1) over --point_range,
+hidden behind the object and the drawn colliders unless --point_xray (--point_hidden_alpha > 0 shows the hidden ones faintly); with --drag the dragged
+point and the cursor get the reference's red and blue discs and the line between them (--no_drag_marker: not).  It composes with --drag, --force,
+--pin_*, --floor, --draw_colliders, --shadows, --bg_radius and --save_*.
 Without --ckpt such a run renders and meshes the SHAPED synthetic checkpoint (its density field has the solid's shape; the plain one's does not).
 Reference: main_gui.py:20-66 (model + simulator construction), nerf/gui.py:556-645 (test_step: IP info -> substep -> render),
 main_render.py:47-104 (frame loop, save_image), simulator/solver.py:109-113 (OutputToPly).
@@ -130,6 +137,32 @@ def configure_shadows(h, args):
         raise SystemExit(f"--shadows: {e}")
 
 
+def point_args_given(args):
+    return (args.point_radius is not None or args.point_color is not None or args.point_mode is not None or args.point_range is not None
+            or args.point_xray or args.point_alpha is not None or args.point_hidden_alpha is not None or args.no_drag_marker)
+
+
+def point_style_from(args):
+    """--point_* as a PointStyle; SystemExit for a value point_style refuses."""
+    from .points_overlay import POINT_RGB, point_style
+    d = lambda v, dflt: dflt if v is None else v
+    lo, hi = args.point_range if args.point_range is not None else (None, None)
+    try:
+        return point_style(radius=d(args.point_radius, 1), mode=d(args.point_mode, "flat"), rgb=d(args.point_color, POINT_RGB), lo=lo, hi=hi,
+                           xray=args.point_xray, alpha=d(args.point_alpha, 1.0), hidden_alpha=d(args.point_hidden_alpha, 0.0))
+    except ValueError as e:
+        raise SystemExit(f"--draw_points: {e}")
+
+
+def configure_points(h, args):
+    """--draw_points and its options as one call on the harness, behind enable_drag (the handle reads the drag state) and the colliders' overlay."""
+    if not args.draw_points:
+        return None
+    style = point_style_from(args)
+    h.draw_points(style, markers=not args.no_drag_marker)
+    return style
+
+
 def check_overlay_args(args):
     """What configure_overlay refuses, before anything is built."""
     if args.draw_colliders and not wants_contact(args):
@@ -140,6 +173,10 @@ def check_overlay_args(args):
         raise SystemExit("--shadows needs --draw_colliders")
     if not args.shadows and (args.light is not None or args.shadow_strength is not None or args.shadow_res is not None):
         raise SystemExit("--light / --shadow_strength / --shadow_res need --shadows")
+    if not args.draw_points and point_args_given(args):
+        raise SystemExit("--point_* / --no_drag_marker need --draw_points")
+    if args.draw_points:
+        point_style_from(args)
 
 
 def run(args):
@@ -167,6 +204,7 @@ def run(args):
             raise SystemExit(f"--pin_shake / --pin_twist: {e}")
     configure_contact(h.sim, args)
     configure_overlay(h, args)
+    configure_points(h, args)
     if args.save_mesh:
         binding, triangles, colors = bind_rest_mesh(h, args)
         if not args.quiet:
@@ -258,6 +296,15 @@ def parser():
     ap.add_argument("--light", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"), help="a vector from the scene towards the light (default: 0.4 1 0.3)")
     ap.add_argument("--shadow_strength", type=float, default=None, metavar="F", help="how dark a full shadow is, in [0, 1] (default 0.6)")
     ap.add_argument("--shadow_res", type=int, default=None, metavar="S", help="texels per side of the light's opacity map, 2 .. 4096 (default 256)")
+    ap.add_argument("--draw_points", action="store_true", help="paint the simulator's integration points (and the drag handle) into every frame (DESIGN.md 4.13)")
+    ap.add_argument("--point_radius", type=int, default=None, metavar="R", help="a point's footprint in pixels, 0 .. 8 (default 1)")
+    ap.add_argument("--point_color", type=float, nargs=3, default=None, metavar=("R", "G", "B"), help="the points' colour in the flat mode (default: 0 0 1)")
+    ap.add_argument("--point_mode", choices=("flat", "strain", "volume"), default=None, help="one colour, or a ramp over the strain norm / the volume change")
+    ap.add_argument("--point_range", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="the ramp's range (default: 0 0.25 for strain, -0.25 0.25 for volume)")
+    ap.add_argument("--point_xray", action="store_true", help="draw every point, also those behind the object (the reference's behaviour)")
+    ap.add_argument("--point_alpha", type=float, default=None, metavar="A", help="the points' opacity, in [0, 1] (default 1)")
+    ap.add_argument("--point_hidden_alpha", type=float, default=None, metavar="A", help="factor on the opacity of a hidden point, in [0, 1] (default 0: not drawn)")
+    ap.add_argument("--no_drag_marker", action="store_true", help="with --drag: no red / blue discs and line on the dragged point")
     ap.add_argument("--save_ply", action="store_true")
     ap.add_argument("--save_ip_state", action="store_true")
     ap.add_argument("--save_mesh", action="store_true", help="write the deforming surface mesh of every frame as OUT/mesh_{f}.ply (rest mesh bound to the simulator, "

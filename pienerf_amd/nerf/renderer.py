@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 
 from .. import raymarching
-from .._lib import ColliderStyle, RenderOpts, ShadowLight, check, lib, ptr, require_gpu, stream_ptr
+from .._lib import ColliderStyle, PointStyle, RenderOpts, ShadowLight, check, lib, ptr, require_gpu, stream_ptr
 from .utils import get_pnts_in_grids
 
 
@@ -80,6 +80,8 @@ class NeRFRenderer(nn.Module):
         self.last_stats = None
         self._overlay = None   # set_collider_overlay: (contact state on the device, ColliderStyle, t_max)
         self._shadows = None   # set_collider_shadows: the light, its rays and the map buffers
+        self._points = None    # set_point_overlay: the camera, the style and what else the point overlay's launch pair reads
+        self._point_keys = {}  # ... and its key buffers, one per frame workspace
 
     def forward(self, x, d):
         raise NotImplementedError()
@@ -218,6 +220,113 @@ class NeRFRenderer(nn.Module):
                                           ptr(weights_sum), ptr(depth_0), ptr(image), ptr(res[0]), ptr(res[1]), stream_ptr()), "draw_colliders")
         return res
 
+    # ------------------------------------------------------------------ the integration points and the drag handle drawn into the frame
+    def set_point_overlay(self, pose_dev, intrinsics, W, H, style=None, source="ip", values=None, drag_state=None):
+        """From now on rund_cuda (render_deformed) and render_continue draw the frame's integration points into the finished picture: a launch pair
+        (pn_draw_points; include/pienerf_hip.h has the law) LAST on the deformed path, behind the colliders' launch and the background's blend, with the
+        colliders' collider_t in its depth test when a collider overlay is set.  `source` 'ip': the positions and deformation gradients are the frame's
+        own p_def / IP_F, so a pipelined frame draws the state it was rendered from.  `pose_dev`: the camera's c2w matrix as a device tensor of 16
+        floats, read at execution time (a captured render follows it); None: every render passes its own as the keyword `point_pose` (the harness's
+        forms do: each pipeline workspace keeps a pose of its own).  `intrinsics` = (fx, fy, cx, cy) and `W`, `H`: the frame's; a render needs
+        N == W H rays.  `style`: a PointStyle (pienerf_amd.points_overlay.point_style; None: its defaults), baked into a captured launch like the
+        intrinsics.  `values`: a device tensor [n] fp32 for the mode 'values'.  `drag_state`: the simulator's device pn_drag_state (5 doubles) — the
+        launch then draws the drag handle while the drag is active.  The returned dict gains 'point_id' [N] int32 (the drawn point per pixel, -1:
+        none) and 'point_t' [N].  The static, hierarchical and op-by-op renders raise while it is set."""
+        from ..points_overlay import mode_name, point_style
+        style = point_style() if style is None else style
+        if not isinstance(style, PointStyle):
+            raise ValueError("set_point_overlay: `style` is a PointStyle (pienerf_amd.points_overlay.point_style)")
+        if source != "ip":
+            raise ValueError(f"set_point_overlay: source must be 'ip' (the frame's integration points), got {source!r}")
+        W, H = int(W), int(H)
+        intr = tuple(float(v) for v in intrinsics)
+        if W <= 0 or H <= 0 or len(intr) != 4 or not all(math.isfinite(v) for v in intr):
+            raise ValueError("set_point_overlay: W, H > 0 and four finite intrinsics (fx, fy, cx, cy)")
+        if pose_dev is not None:
+            self._check_point_pose(pose_dev)
+        if mode_name(style) == "values":
+            if not (torch.is_tensor(values) and values.dtype == torch.float32 and values.dim() == 1 and values.is_contiguous()):
+                raise ValueError("set_point_overlay: the mode 'values' needs `values`, a contiguous fp32 tensor [n] on the GPU")
+            require_gpu(values)
+        elif values is not None:
+            raise ValueError("set_point_overlay: `values` goes with the mode 'values'")
+        if drag_state is not None:
+            if not (torch.is_tensor(drag_state) and drag_state.dtype == torch.float64 and drag_state.numel() == 5 and drag_state.is_contiguous()):
+                raise ValueError("set_point_overlay: `drag_state` is a contiguous tensor of 5 doubles (pn_drag_state; the simulator's own)")
+            require_gpu(drag_state)
+        self._points = {"pose": pose_dev, "intr": intr, "intr_c": (C.c_float * 4)(*intr), "W": W, "H": H, "style": style, "values": values,
+                        "drag": drag_state}
+        return self
+
+    @staticmethod
+    def _check_point_pose(pose):
+        if not (torch.is_tensor(pose) and pose.dtype == torch.float32 and pose.numel() == 16 and pose.is_contiguous()):
+            raise ValueError("point overlay: the pose is a contiguous fp32 tensor of 16 values (c2w, row-major) on the GPU")
+        require_gpu(pose)
+
+    def clear_point_overlay(self):
+        self._points = None
+
+    def point_overlay_key(self):
+        """What a captured render bakes in of the point overlay (None without one): the intrinsics, W, H, the style's bytes and the addresses of the
+        default pose, the values and the drag state."""
+        if self._points is None:
+            return None
+        p = self._points
+        adr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        return (adr(p["pose"]), p["intr"], p["W"], p["H"], bytes(p["style"]), adr(p["values"]), adr(p["drag"]))
+
+    def point_overlay_reads_drag(self):
+        """Whether the launch pair reads a drag state: the caller then orders the render behind the stream that writes it."""
+        return self._points is not None and self._points["drag"] is not None
+
+    def _refuse_point_overlay(self, what):
+        if self._points is not None:
+            raise RuntimeError(f"point overlay: {what} does not draw the points — only the deformed path does (render_deformed / rund_cuda without "
+                               "perturb, and render_continue); clear_point_overlay() first")
+
+    def _point_key_buffer(self, slot, device):
+        """The key buffer of frame workspace `slot` (lanes run concurrently: one each), allocated and filled outside any capture."""
+        from ..points_overlay import key_buffer
+        p = self._points
+        cur = self._point_keys.get(slot)
+        if cur is None or cur.numel() != p["W"] * p["H"] or cur.device != device:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f"point overlay: the key buffer of frame workspace {slot} must exist before a capture: render one frame on it first")
+            cur = self._point_keys[slot] = key_buffer(p["W"], p["H"], device)
+        return cur
+
+    def _draw_points(self, p_def, F_IP, weights_sum, depth_0, collider_t, image, out, ob, kwargs):
+        """Enqueues the point overlay's launch pair on the current stream, in place in `image` (the finished picture); 'point_id' and 'point_t' of `out`
+        (then of `ob`, else allocated) receive its other outputs.  Returns (point_id, point_t)."""
+        p = self._points
+        N = image.shape[0]
+        if N != p["W"] * p["H"]:
+            raise RuntimeError(f"point overlay: set for a {p['W']} x {p['H']} frame, this render has {N} rays (it needs N == W H: the whole image)")
+        pose = kwargs.get("point_pose")
+        pose = p["pose"] if pose is None else pose
+        if pose is None:
+            raise RuntimeError("point overlay: set_point_overlay() got no pose_dev: pass this render's camera as point_pose=")
+        self._check_point_pose(pose)
+        n = p_def.shape[0]
+        if p["values"] is not None and p["values"].shape[0] != n:
+            raise RuntimeError(f"point overlay: `values` has {p['values'].shape[0]} entries, the frame {n} integration points")
+        assert F_IP.shape[0] == n and F_IP.is_contiguous() and image.is_contiguous()
+        res = []
+        for name, dtype in (("point_id", torch.int32), ("point_t", torch.float32)):
+            t = out.get(name) if out is not None else None
+            if t is None and ob is not None:
+                t = ob.get(name)
+            if t is None:
+                t = torch.empty(N, dtype=dtype, device=image.device)
+            assert t.shape == (N,) and t.dtype == dtype and t.is_contiguous()
+            res.append(t)
+        keys = self._point_key_buffer(int(kwargs.get("frame_slot") or 0), image.device)
+        check(lib().pn_draw_points(ptr(p_def), ptr(F_IP), ptr(p["values"]), n, ptr(pose), p["intr_c"], p["W"], p["H"], float(self.min_near),
+                                   ptr(weights_sum), ptr(depth_0), ptr(collider_t), ptr(p["drag"]), ptr(keys), p["style"], ptr(image), ptr(res[0]),
+                                   ptr(res[1]), stream_ptr()), "draw_points")
+        return res
+
     # ------------------------------------------------------------------ entry point (renderer.py:587-599)
     def render_deformed(self, rays_o, rays_d, staged=False, max_ray_batch=4096, **kwargs):
         """renderer.py:587-599.  `staged` / `max_ray_batch` are accepted and unused exactly as in the reference, whose render_deformed calls
@@ -300,6 +409,7 @@ class NeRFRenderer(nn.Module):
     def rund_cuda(self, rays_o, rays_d, dt_gamma=0, bg_color=None, perturb=False, max_steps=1024, T_thresh=1e-2, **kwargs):
         if perturb:
             self._refuse_overlay("the op-by-op loop (perturb=True)")
+            self._refuse_point_overlay("the op-by-op loop (perturb=True)")
             return self.rund_cuda_ops(rays_o, rays_d, dt_gamma, bg_color, perturb, max_steps, T_thresh, **kwargs)
         prefix = rays_o.shape[:-1]
         rays_o, rays_d = _flat_rays(rays_o, rays_d)
@@ -358,6 +468,8 @@ class NeRFRenderer(nn.Module):
             self.blend_background(rays_o, rays_d, covered, image)   # in place: `image` may be the caller's out_buffers
         elif bg_tensor is not None:
             image = image + (1 - covered).unsqueeze(-1) * bg_tensor
+        if self._points is not None and not shadow_pass:   # last: the points and the drag handle, painted onto the finished picture
+            res["point_id"], res["point_t"] = self._draw_points(p_def, F_IP, weights_sum, depth_0, res.get("collider_t"), image, None, ob, kwargs)
         res["image"] = image.view(*prefix, 3)
         return res
 
@@ -386,6 +498,7 @@ class NeRFRenderer(nn.Module):
                 self.last_stats = keep
         if static:
             self._refuse_overlay("the static render (render_continue with static=True)")
+            self._refuse_point_overlay("the static render (render_continue with static=True)")
             o = self._static_opts(dt_gamma, 1 if bg_color is None else bg_color, max_steps, T_thresh)
         else:
             # with an overlay the epilogue rewrites `image` from the driver's accumulator over 0 and the overlay is applied once more, below
@@ -408,6 +521,13 @@ class NeRFRenderer(nn.Module):
                 out["shadow"] = drawn[2]
         if self.bg_radius > 0 and not shadow_pass:
             self.blend_background(rays_o, rays_d, covered, image)
+        if self._points is not None and not shadow_pass and not static:
+            # the epilogue rewrote `image`: the points are painted again, from the state the frame was rendered from (the key buffer cleaned itself)
+            if "depth_0" not in out:
+                raise RuntimeError("render_continue: the point overlay tests against depth_0: pass the dict the deformed render returned")
+            p_def, _, F_IP, _ = self._ip_state(image.device)
+            out["point_id"], out["point_t"] = self._draw_points(p_def, F_IP, ws, depth_0, out.get("collider_t") if overlay else None, image, out, None,
+                                                                dict(kwargs, frame_slot=slot))
         if stats is not None:
             self._set_stats(stats)
         return out
@@ -481,6 +601,7 @@ class NeRFRenderer(nn.Module):
                   synchronises the host on every trip, :351-380).  Per-ray background colours and ``perturb`` take the op-by-op loop
                   ``run_cuda_ops`` (same kernels, host-driven)."""
         self._refuse_overlay("the static render (run_cuda)")
+        self._refuse_point_overlay("the static render (run_cuda)")
         if not self.training and not perturb and (self.bg_radius > 0 or not torch.is_tensor(bg_color)):
             return self._run_static_fused(rays_o, rays_d, dt_gamma, 1 if bg_color is None else bg_color, max_steps, T_thresh, **kwargs)
         return self.run_cuda_ops(rays_o, rays_d, dt_gamma, bg_color, perturb, force_all_rays, max_steps, T_thresh, **kwargs)
@@ -519,6 +640,7 @@ class NeRFRenderer(nn.Module):
     def run_cuda_ops(self, rays_o, rays_d, dt_gamma=0, bg_color=None, perturb=False, force_all_rays=False, max_steps=1024, T_thresh=1e-2, **kwargs):
         """run_cuda op by op on the drop-in ops (the training branch; the eval branch with perturb / tensor backgrounds; parity tests)."""
         self._refuse_overlay("the static render (run_cuda_ops)")
+        self._refuse_point_overlay("the static render (run_cuda_ops)")
         shape = rays_o.shape[:-1]
         o3, d3 = rays_o.contiguous().view(-1, 3), rays_d.contiguous().view(-1, 3)
         nears, fars = raymarching.near_far_from_aabb(o3, d3, self.aabb_train if self.training else self.aabb_infer, self.min_near)
@@ -611,6 +733,7 @@ class NeRFRenderer(nn.Module):
         otherwise (train() mode, autograd recording, perturb, fp16 autocast — there is no half form of the launch —, or
                   num_steps + upsample_steps beyond the launch's LDS-resident limit, pn_hier_max_samples() = 512):  ``run_ops``."""
         self._refuse_overlay("the hierarchical render (run)")
+        self._refuse_point_overlay("the hierarchical render (run)")
         self._check_hier_steps(num_steps, upsample_steps)
         if self._hier_fused_ok(rays_o, num_steps, upsample_steps, bg_color, perturb):
             return self._run_hier_fused(rays_o, rays_d, int(num_steps), int(upsample_steps), bg_color)
@@ -642,6 +765,7 @@ class NeRFRenderer(nn.Module):
         """``run`` as the reference's op sequence on near_far_from_aabb / density / color / sample_pdf and torch ops: differentiable (the training
         branch), with perturb, under autocast, with any background; the parity tests pin it against the reference's own run."""
         self._refuse_overlay("the hierarchical render (run_ops)")
+        self._refuse_point_overlay("the hierarchical render (run_ops)")
         self._check_hier_steps(num_steps, upsample_steps)
         prefix = rays_o.shape[:-1]
         rays_o = rays_o.contiguous().view(-1, 3)
@@ -758,6 +882,7 @@ class NeRFRenderer(nn.Module):
     # ------------------------------------------------------------------ op-by-op loop (reference structure, renderer.py:755-907)
     def rund_cuda_ops(self, rays_o, rays_d, dt_gamma=0, bg_color=None, perturb=False, max_steps=1024, T_thresh=1e-2, **kwargs):
         self._refuse_overlay("the op-by-op loop (rund_cuda_ops)")
+        self._refuse_point_overlay("the op-by-op loop (rund_cuda_ops)")
         dtype = torch.float32
         prefix = rays_o.shape[:-1]
         rays_o = rays_o.contiguous().view(-1, 3)
