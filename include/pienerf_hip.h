@@ -891,6 +891,37 @@ int pn_ssim_forward(const float* pred, const float* truth, int B, int H, int W, 
 int pn_ssim_backward(const float* pred, const float* truth, int B, int H, int W, int C, const float* mapA, const float* mapB, const float* mapD,
                      const float* grad_out, float* grad_pred, void* stream);
 
+/* ------------------------------------------------------------------ video ---- */
+
+/* A frame as a baseline sequential JPEG (SOF0, 8 bit, 3 components, interleaved), encoded on the device (csrc/pn_jpeg.hip, pienerf_amd/video.py,
+ * DESIGN.md 4.14).  `image` [H, W, 3] fp32 on the device, as the renderer leaves it.  Written: the entropy-coded scan — everything between the SOS
+ * header and EOI, restart markers included — to stream_out, and its length in bytes to *nbytes_out (both device memory); the host prepends the
+ * header (video.jpeg_header) and appends EOI.  subsampling: 420 (MCU 16 x 16: Y00 Y01 Y10 Y11 Cb Cr) or 444 (MCU 8 x 8: Y Cb Cr).
+ * The arithmetic, all fp32, one rounding per operation, sums left to right (tests/jpeg_reference.py restates it; the bytes agree):
+ *   pixel     c = isnan(v) ? 0 : min(max(v, 0), 1), p = floorf(c * 255.0f) (io.save_image's truncation); a frame whose W or H is no multiple of the
+ *             MCU is padded by replicating its last column and row;
+ *   colour    Y = 0.299f R + 0.587f G + 0.114f B - 128.0f, Cb = -0.168735892f R - 0.331264108f G + 0.5f B,
+ *             Cr = 0.5f R - 0.418687589f G - 0.081312411f B; a 4:2:0 chroma sample is ((tl + tr) + (bl + br)) * 0.25f of the converted values;
+ *   DCT       t[y][u] = sum_x s[y][x] C[u][x], then d[v][u] = sum_y C[v][y] t[y][u], C[u][x] = (float)(c(u) / 2 cos((2x + 1) u pi / 16)) from fp64
+ *             (csrc/pn_jpeg_tables.h);
+ *   quantise  q = rintf(d / (float)Q[k]), ties to even; AC values clamped to +-1023, DC differences to +-2047 (baseline's categories);
+ *   entropy   the typical Huffman tables of T.81 Annex K; one restart interval per MCU row (DRI = MCUs per row), the DC predictors reset at each;
+ *             an interval is padded with 1-bits to a byte, a 0x00 follows every 0xFF byte, and FF D0+(r mod 8) follows interval r but the last.
+ * The two quantisation tables (64 entries of 1 .. 255, natural order, HOST memory) are read during the call and travel by value in the launch.
+ * Three launches on `stream`; no allocation, no host synchronisation, no host-visible side effect: legal inside a stream capture, and a captured launch
+ * keeps the tables it was captured with.  Equal inputs give equal bytes.
+ * PN_ERR_ARG before anything is enqueued for: a NULL pointer; W or H of 0 or above 65535; another subsampling; a frame whose bound below does not fit the
+ * 32-bit count; a table entry of 0; capacity below pn_jpeg_stream_capacity; `work` not 16-byte aligned; stream_out, work or nbytes_out overlapping image
+ * or each other. */
+/* A proven bound on the scan's bytes: a block is at most 20 + 63 * 26 bits < 208 bytes, doubled by stuffing: n_blocks * 416 + 2 (mcu_rows - 1).  The
+ * encoder requires this capacity and cannot pass it; there is no overflow flag.  0 for arguments pn_jpeg_encode refuses. */
+uint64_t pn_jpeg_stream_capacity(uint32_t W, uint32_t H, int subsampling);
+/* Bytes of `work` (16-byte aligned): the coefficients, the intervals' bit staging and stuffed segments (both sized from the worst case) and their
+ * offsets.  Nothing in it outlives the call's launches.  0 for arguments pn_jpeg_encode refuses. */
+uint64_t pn_jpeg_work_bytes(uint32_t W, uint32_t H, int subsampling);
+int pn_jpeg_encode(const float* image, uint32_t W, uint32_t H, int subsampling, const uint8_t* qtab_luma_host64, const uint8_t* qtab_chroma_host64,
+                   void* work, uint8_t* stream_out, uint64_t capacity, uint32_t* nbytes_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -162,6 +162,9 @@ SIGNATURES = {
     "pn_ssim_range": (i32, [P, P, u64, f32, P, P, P]),
     "pn_ssim_forward": (i32, [P, P, i32, i32, i32, i32, P, P, P, P, P, P, P]),
     "pn_ssim_backward": (i32, [P, P, i32, i32, i32, i32, P, P, P, P, P, P]),
+    "pn_jpeg_stream_capacity": (u64, [u32, u32, i32]),
+    "pn_jpeg_work_bytes": (u64, [u32, u32, i32]),
+    "pn_jpeg_encode": (i32, [P, u32, u32, i32, P, P, P, P, u64, P, P]),
 }
 
 _lib = None

@@ -63,6 +63,9 @@ UNITS = {
     # SSIM (metrics.py): every moment is a sum of 11 products in tap order and sigma = E[xx] - mx^2 cancels, so each operation rounds once as written;
     # tests/ssim_reference.py's fp32 evaluation then has the same error size and sets the tests' tolerance
     "pn_ssim.hip": ["-ffp-contract=off"],
+    # baseline JPEG of a frame (video.py): colour transform, DCT and quantisation decide integers, so every operation rounds once in source order;
+    # tests/jpeg_reference.py restates them in numpy and the encoded bytes agree
+    "pn_jpeg.hip": ["-ffp-contract=off"],
     "pn_copier.hip": [],  # host code only: frame copies through the HSA runtime (links libhsa-runtime64)
 }
 

@@ -10,6 +10,7 @@ deformed point cloud and the per-frame IP state the reference's ``main_render.py
            [--draw_points [--point_radius 1] [--point_color R G B] [--point_mode flat|strain|volume] [--point_range LO HI] [--point_xray]
            [--point_alpha 1] [--point_hidden_alpha 0] [--no_drag_marker]]
            [--save_mesh [--mesh_resolution 128] [--mesh_threshold 10] [--mesh_con 0] [--mesh_normals] [--mesh_color]]
+           [--video [PATH] [--fps 30] [--video_quality 90] [--video_subsampling 420|444] [--no_png]]
 
 Without --ply / --ckpt the synthetic chair of pienerf_amd.scene is used (there are no assets on the GPU box).
 --save_mesh writes the deforming surface: the model's density level set, meshed once at rest, bound to the simulator (Simulator.bind_points) and warped
@@ -31,7 +32,11 @@ checkbox: discs of --point_radius pixels in --point_color, or coloured by --poin
 hidden behind the object and the drawn colliders unless --point_xray (--point_hidden_alpha > 0 shows the hidden ones faintly); with --drag the dragged
 point and the cursor get the reference's red and blue discs and the line between them (--no_drag_marker: not).  It composes with --drag, --force,
 --pin_*, --floor, --draw_colliders, --shadows, --bg_radius and --save_*.
-Without --ckpt such a run renders and meshes the SHAPED synthetic checkpoint (its density field has the solid's shape; the plain one's does not).
+--video writes the run as one MJPEG AVI (pienerf_amd/video.py; default OUT/video.avi) that any player opens: every frame is encoded as a
+baseline JPEG on the device, from the tensor the step returns, and only the finished bitstream crosses to the host; frame f of the video is the JPEG of
+img_f.png's pixels.  --no_png leaves the PNGs out, and then the fp32 image is not copied to the host at all.  It composes with every other flag (the
+overlays are part of the image).  python -m pienerf_amd.video OUT/video.avi --extract DIR writes the frames out as .jpg files.
+Without --ckpt a --save_mesh run renders and meshes the SHAPED synthetic checkpoint (its density field has the solid's shape; the plain one's does not).
 Reference: main_gui.py:20-66 (model + simulator construction), nerf/gui.py:556-645 (test_step: IP info -> substep -> render),
 main_render.py:47-104 (frame loop, save_image), simulator/solver.py:109-113 (OutputToPly).
 """
@@ -179,7 +184,57 @@ def check_overlay_args(args):
         point_style_from(args)
 
 
+def check_video_args(args):
+    """What --video and its options refuse, before anything is built."""
+    if args.video is None:
+        if args.no_png:
+            raise SystemExit("--no_png needs --video: the run would write no frame at all")
+        return
+    from .video import quant_tables
+    try:
+        quant_tables(args.video_quality)
+    except ValueError as e:
+        raise SystemExit(f"--video_quality: {e}")
+    if not args.fps > 0:
+        raise SystemExit("--fps is positive")
+
+
+def video_path(args):
+    """Where --video writes: its argument, or OUT/video.avi; None without --video."""
+    if args.video is None:
+        return None
+    return args.video or os.path.join(args.out, "video.avi")
+
+
+class FrameVideo:
+    """The frames of a run as a video file: add(image) encodes the device tensor a step returned (JpegEncoder) and appends the JPEG (AviWriter)."""
+
+    def __init__(self, path, W, H, fps=30, quality=90, subsampling="420", device="cuda"):
+        from .video import AviWriter, JpegEncoder
+        self.encoder = JpegEncoder(W, H, quality=quality, subsampling=subsampling, device=device)
+        self.avi = AviWriter(path, W, H, fps)
+        self.path, self.bytes = path, 0
+
+    def add(self, image):
+        data = self.encoder.encode(image)
+        self.avi.add(data)
+        self.bytes += len(data)
+        return data
+
+    def close(self):
+        self.avi.close()
+
+
+def open_video(args, device):
+    """--video and its options as a FrameVideo; None without --video."""
+    path = video_path(args)
+    if path is None:
+        return None
+    return FrameVideo(path, args.W, args.H, fps=args.fps, quality=args.video_quality, subsampling=args.video_subsampling, device=device)
+
+
 def run(args):
+    check_video_args(args)
     if args.pin_centre is not None and args.pin_twist is None:
         raise SystemExit("--pin_centre is the centre of --pin_twist")
     check_overlay_args(args)
@@ -209,6 +264,7 @@ def run(args):
         binding, triangles, colors = bind_rest_mesh(h, args)
         if not args.quiet:
             print(f"mesh: {binding.V} vertices, {len(triangles)} triangles; {binding.n_fallback} vertices bound through their nearest integration point")
+    video = open_video(args, h.device)
     written, t0 = [], time.time()
     for f in range(args.frames):
         if args.drag is not None:
@@ -227,10 +283,14 @@ def run(args):
             pos, nrm = w if args.mesh_normals else (w, None)
             scene.write_mesh_ply(os.path.join(args.out, f"mesh_{f}.ply"), pos.cpu().numpy(), triangles,
                                  normals=nrm.cpu().numpy() if nrm is not None else None, colors=colors)
-        out = h.to_host(h.step(pose=pose, collect_stats=True))
-        path = os.path.join(args.out, f"img_{f}.png")
-        io.save_image(out["image"], path, args.W, args.H)
-        written.append(path)
+        out = h.step(pose=pose, collect_stats=True)
+        if video is not None:   # from the device tensor, before the host copy: the bitstream crosses, not the floats
+            video.add(out["image"])
+        if not args.no_png:
+            out = h.to_host(out)
+            path = os.path.join(args.out, f"img_{f}.png")
+            io.save_image(out["image"], path, args.W, args.H)
+            written.append(path)
         if args.save_ip_state:  # what gui.py dumps and main_render.py:90-100 reads back
             m = h.model
             for name, t in (("ip_pos", m.p_def), ("ip_F", m.IP_F), ("ip_dF", m.IP_dF)):
@@ -239,6 +299,10 @@ def run(args):
             h.synchronize()
             h.sim.OutputToPly(os.path.join(args.out, f"points_{f}.ply"))
     h.synchronize()
+    if video is not None:
+        video.close()
+        if not args.quiet:
+            print(f"video: {args.frames} frames, {video.bytes} bytes of JPEG -> {os.path.abspath(video.path)}")
     if h.sim.contact_enabled and not args.quiet:
         print(f"contact: {h.sim.contact_count()} of {h.sim.n_IP} integration points in contact in the last substep")
     if not args.quiet:
@@ -314,6 +378,12 @@ def parser():
     ap.add_argument("--mesh_con", type=int, default=0, help="mesh only this many largest connected components (0: everything)")
     ap.add_argument("--mesh_normals", action="store_true", help="write per-frame vertex normals (rest normals pushed forward by cof(F))")
     ap.add_argument("--mesh_color", action="store_true", help="write vertex colours, computed once at rest (the model's colour seen along -normal)")
+    ap.add_argument("--video", nargs="?", const="", default=None, metavar="PATH",
+                    help="write the run as an MJPEG AVI, every frame JPEG-encoded on the device (DESIGN.md 4.14); default PATH: OUT/video.avi")
+    ap.add_argument("--fps", type=float, default=30, help="the video's frame rate")
+    ap.add_argument("--video_quality", type=int, default=90, help="JPEG quality of the video's frames, 1 .. 100 (libjpeg's scale)")
+    ap.add_argument("--video_subsampling", choices=("420", "444"), default="420", help="chroma at half resolution on both axes, or at full resolution")
+    ap.add_argument("--no_png", action="store_true", help="with --video: write no img_{f}.png, and copy no fp32 image to the host")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--quiet", action="store_true")
     return ap
