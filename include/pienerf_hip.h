@@ -657,6 +657,62 @@ int pn_sim_contact_rhs(int n_k, int n_IP, const void* state, double dt, double d
                        const double* rho, const double* Nx, const int* kernel_bg, const int* kernel_cnt, const int* buffer, const double* Nx_csr,
                        const double* rhs_in, double* rhs_out, double* accel_out, void* stream);
 
+/* Force fields (csrc/pn_fields.hip; Simulator.enable_fields): wind, vortex and blast on the whole body, with air drag.  A fourth
+ * right-hand-side stage beside drag, pins and contact: launches in front of every substep write rhs_out = rhs_in + the field term of the state and the
+ * time that substep starts from, and the substep takes rhs_out in its rhs_gravity slot; the matrix, Ainv and the substep's kernels stay as they are.
+ * All fp64.  Substep k of the stage's own clock uses t = k dt.  x_i, v_i and m_i as for contact (above).  The fields 0 .. n-1 are visited in index
+ * order, each acting only while t0 <= t < t1 (t1 may be +inf).  With c_eff = min(c, 1/dt), fall(q) = max(1 - q/R, 0)^2 and
+ * s_eff = sign(s) min(|s|, R / (2 dt^2)):
+ *     wind (origin p, velocity W = n, drag c, gust g, f, phi, wave vector kv):
+ *         u = W (1 + g sin(2 pi (f t - kv.(x - p)) + phi)),   a_i += c_eff (u - v)          W = 0: still-air drag, mass-proportional damping
+ *     vortex (point p, unit axis n, angular speed omega = s, drag c, R):
+ *         r = x - p, rho = |r - (n.r) n|,   a_i += c_eff fall(rho) (omega (n x r) - v)      continuous at rho = R, exactly nothing at and beyond it
+ *     radial (centre p, strength s in acceleration units, away for s > 0, R):
+ *         L = |x - p|,   a_i += s_eff fall(L) (x - p) / L                                   only when L > 0; exactly nothing at and beyond R
+ *     rhs_out[k 30 + j 3 + r] = rhs_in[...] + sum_e m_i Nx[i,slot,j] a_i[r]  over the (i, slot) entries e of kernel k's run, ascending.
+ * The system matrix is at least M / dt^2, so a point's own response per step is at most dt c_eff |u - v| <= |u - v| in velocity, and at most R / 2 in
+ * position for the radial field: the two clamps are the stability bounds.  Layout of the state: */
+#define PN_FIELD_SLOTS 8
+enum { PN_FIELD_EMPTY = 0, PN_FIELD_WIND = 1, PN_FIELD_VORTEX = 2, PN_FIELD_RADIAL = 3 };
+typedef struct pn_force_field {        /* 144 bytes */
+    int type;          /* PN_FIELD_*; 0: the slot is empty */
+    int reserved;
+    double p[3];       /* wind: origin of the gust's wave; vortex: a point of the axis; radial: the centre */
+    double n[3];       /* wind: the velocity W; vortex: the unit axis */
+    double c;          /* drag, 1/s, >= 0 (wind, vortex) */
+    double s;          /* vortex: omega, rad/s; radial: strength, acceleration units */
+    double R;          /* radius, > 0 (vortex, radial) */
+    double g, f, phi;  /* wind: gust depth in [0, 1], frequency in Hz, phase */
+    double kv[3];      /* wind: the gust's wave vector, cycles per unit length */
+    double t0, t1;     /* acts while t0 <= t < t1; t1 may be +inf */
+} pn_force_field;
+typedef struct pn_field_state {        /* 1168 bytes = 146 doubles */
+    int64_t k;         /* substeps since the last pn_sim_fields_clock */
+    int active;        /* 0: rhs_out = rhs_in, bit for bit */
+    int n;             /* 1 + the highest slot in use (<= 8); 0: rhs_out = rhs_in, bit for bit */
+    pn_force_field f[PN_FIELD_SLOTS];
+} pn_field_state;
+uint64_t pn_sim_fields_bytes(void);      /* sizeof(pn_field_state) = 1168 */
+/* active = 0 or 1, else PN_ERR_ARG.  A one-thread launch on `stream`; the clock and the slots are left alone. */
+int pn_sim_fields_set_active(void* state, int active, void* stream);
+/* Writes slot `index` (0 .. 7) and recomputes n.  geom17_host = (p[3], n[3], c, s, R, g, f, phi, kv[3], t0, t1).  PN_ERR_ARG, before anything is
+ * enqueued, for an index outside 0 .. 7, an unknown type, a non-finite value (only t1 may be +inf), c < 0, g outside [0, 1], R <= 0 for a vortex or a
+ * radial field, a vortex axis that is not a unit vector to 1e-9, t1 < t0.  Type PN_FIELD_EMPTY clears the slot (geom17_host may be NULL).  A
+ * one-thread launch on `stream`. */
+int pn_sim_fields_set_field(void* state, int index, int type, const double* geom17_host, void* stream);
+/* k = the clock's new value (>= 0), by a one-thread launch on `stream`. */
+int pn_sim_fields_clock(void* state, int64_t k, void* stream);
+/* rhs_out [10 n_k,3] = rhs_in + the field term at t = k dt, then k += 1; rhs_in is left untouched and rhs_out is another buffer.  The tables are
+ * pn_sim_contact_rhs's.  THREE launches: a thread per point writes accel_out [n_IP,3] = a_i (one wave per workgroup); a workgroup of four waves per
+ * kernel, thread t taking the run's entries t, t + 256, ... in ascending order, adds m_i Nx a_i: shuffle tree 32 ... 1 per wave, then the waves in
+ * order through LDS, no atomics — the order and the reduction of pn_sim_contact_rhs's second launch; and a one-thread launch BEHIND them advances the
+ * clock (no workgroup reads a clock that its own launch advances).  A kernel none of whose points has a != 0, and every kernel when !active, n == 0 or
+ * t is outside every window, copies rhs_in bit for bit (-0.0 included).  PN_ERR_ARG for a NULL pointer, rhs_in == rhs_out, dt or dx not > 0.  No
+ * allocation, no host synchronisation, capturable. */
+int pn_sim_fields_rhs(int n_k, int n_IP, void* state, double dt, double dx, const double* dof, const double* dof_vel, const int* topo,
+                      const double* rho, const double* Nx, const int* kernel_bg, const int* kernel_cnt, const int* buffer, const double* Nx_csr,
+                      const double* rhs_in, double* rhs_out, double* accel_out, void* stream);
+
 /* The colliders drawn into a rendered frame (csrc/pn_colliders.hip; NeRFRenderer.set_collider_overlay): one launch behind the frame
  * driver, a thread per ray, composites the analytic surfaces of a pn_contact_state into `image` with a depth test against the object.  `contact_state`
  * is DEVICE memory with the pn_contact_state layout (the simulator's own buffer or a 744-byte copy), read at execution time: a captured launch follows

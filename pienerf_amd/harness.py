@@ -177,7 +177,7 @@ class SimRenderHarness:
             self._sim_stream = torch.cuda.Stream(self.device)
         self._graph_pose = torch.from_numpy(np.asarray(self.pose, np.float32)).unsqueeze(0).to(self.device)
         self._graph_pose_host = self.pose
-        keep = (self.sim.dof.clone(), self.sim.dof_vel.clone(), self.sim._pin_clock_keep())
+        keep = (self.sim.dof.clone(), self.sim.dof_vel.clone(), self.sim._pin_clock_keep(), self.sim._field_clock_keep())
         warm = torch.cuda.Stream(self.device)
         warm.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(warm):
@@ -191,12 +191,14 @@ class SimRenderHarness:
         self.sim.dof.copy_(keep[0])       # warm-up advanced the simulator; capture itself executes nothing
         self.sim.dof_vel.copy_(keep[1])
         self.sim._pin_clock_restore(keep[2])   # ... the pin motion's substep clock: the k-th replayed frame sees the clock of the k-th eager step
+        self.sim._field_clock_restore(keep[3])   # ... and the force fields' clock
         self.sim.reset_warm_start()       # ... and its SVD warm start: a replay from here has the bits of a simulator that never warmed up
         self._graph_trips = n_trips
         self._graph_done = None
         self._graph_drag = self.sim.drag_enabled   # the substep's k_drag_force launch is in the graph or it is not
         self._graph_pins = self.sim.pin_enabled    # ... and so is its k_pin_rhs launch (Simulator.enable_pin_motion)
         self._graph_contact = self.sim.contact_enabled   # ... and its contact launches (Simulator.enable_contact)
+        self._graph_fields = self.sim.fields_enabled     # ... and its force-field launches (Simulator.enable_fields)
         self._graph_overlay = self.model.collider_overlay_key()   # ... and the render's collider overlay, with its style (draw_colliders)
         self._graph_points = self.model.point_overlay_key()   # ... and the point overlay's launch pair (draw_points)
         self._graph_form_epoch = self._net_form_epoch()
@@ -222,6 +224,11 @@ class SimRenderHarness:
         """Colliders and parameters changed after a capture need no recapture (the state is device memory); the launch itself must be in the graph."""
         if self.sim.contact_enabled and not captured:
             raise RuntimeError(f"contact: {what} was captured before enable_contact(), its substep ignores the colliders: {again} again")
+
+    def _check_fields_captured(self, captured, what, again):
+        """Fields and the clock changed after a capture need no recapture (the state is device memory); the launches themselves must be in the graph."""
+        if self.sim.fields_enabled and not captured:
+            raise RuntimeError(f"fields: {what} was captured before enable_fields(), its substep ignores the force fields: {again} again")
 
     def _check_overlay_captured(self, captured, what, again):
         """The colliders' state is device memory and is followed without a recapture; the overlay's launch, its style and t_max are in the graph."""
@@ -353,6 +360,7 @@ class SimRenderHarness:
         self._check_net_form(self._graph_form_epoch, "the step")
         self._check_pins_captured(self._graph_pins, "the step graph", "capture()")
         self._check_contact_captured(self._graph_contact, "the step graph", "capture()")
+        self._check_fields_captured(getattr(self, "_graph_fields", False), "the step graph", "capture()")
         self._check_overlay_captured(self._graph_overlay, "the step graph", "capture()")
         self._check_points_captured(getattr(self, "_graph_points", None), "the step graph", "capture()")
         self._check_previous_graph_frame()
@@ -468,6 +476,7 @@ class SimRenderHarness:
         self._pipe_drag = self.sim.drag_enabled
         self._pipe_pins = self.sim.pin_enabled
         self._pipe_contact = self.sim.contact_enabled
+        self._pipe_fields = self.sim.fields_enabled
         self._pipe_overlay = self.model.collider_overlay_key()
         self._pipe_points = self.model.point_overlay_key()
         self._pipe_single = not frame_parallel and not (render_kw or {}).get("ray_batch")
@@ -486,6 +495,7 @@ class SimRenderHarness:
         self._check_net_form(self._pipe_form_epoch, "the pipeline")
         self._check_pins_captured(self._pipe_pins, "the pipeline", "capture_pipelined()")
         self._check_contact_captured(self._pipe_contact, "the pipeline", "capture_pipelined()")
+        self._check_fields_captured(getattr(self, "_pipe_fields", False), "the pipeline", "capture_pipelined()")
         if not getattr(self, "_pipe_single", True):
             self._refuse_overlay_form("the frame-parallel / staged pipeline")
             self._refuse_points_form("the frame-parallel / staged pipeline")
@@ -815,7 +825,7 @@ class _HipBackend:
         self.pose_pin = [pose0.clone().pin_memory() for _ in range(n_ws)]
         self.pose_key = [pose0.numpy().tobytes()] * n_ws
         self.ip = [tuple(torch.empty((n_IP, c), dtype=torch.float32, device=dev) for c in (3, 9, 27)) for _ in range(n_ws)]
-        keep = (sim.dof.clone(), sim.dof_vel.clone(), sim._pin_clock_keep())
+        keep = (sim.dof.clone(), sim.dof_vel.clone(), sim._pin_clock_keep(), sim._field_clock_keep())
         main = torch.cuda.current_stream(dev)
         for ws in range(n_ws):  # warm-up of every workspace outside capture (creates the pn_frame workspaces, the fp16 tables, ...)
             s = self._streams[f"lane{ws // depth}"]
@@ -886,7 +896,8 @@ class _HipBackend:
         sim.dof.copy_(keep[0])      # warm-up advanced the simulator; capture itself executes nothing
         sim.dof_vel.copy_(keep[1])
         sim._pin_clock_restore(keep[2])   # ... the pin motion's substep clock
-        sim.reset_warm_start()      # ... and its SVD warm start: a replay from here has the bits of a simulator that never warmed up
+        sim._field_clock_restore(keep[3])   # ... and the force fields'
+        sim.reset_warm_start()     # ... and its SVD warm start: a replay from here has the bits of a simulator that never warmed up
         torch.cuda.synchronize(dev)
 
     def _ws_kw(self, ws):

@@ -5,7 +5,9 @@ deformed point cloud and the per-frame IP state the reference's ``main_render.py
     python -m pienerf_amd.main_render --frames 30 --out output_img/chair [--ply model/chair_0.ply] [--ckpt ws/checkpoints/ngp_ep0300.pth]
            [--W 800 --H 800] [--radius 5 --azimuth 0 --elevation 0 --fovy 50] [--force fx fy fz | --drag X0 Y0 X1 Y1] [--pin_shake AX AY AZ HZ] [--pin_twist NX NY NZ DEG HZ [--pin_centre X Y Z]] [--save_ply] [--save_ip_state]
            [--floor Y] [--collide_sphere CX CY CZ R]... [--collide_inside CX CY CZ R] [--contact_stiffness 0.5 --contact_damping 0.5 --friction 0.5
-           --contact_thickness DX/2] [--unpin] [--draw_colliders [--collider_color R G B]... [--checker S]
+           --contact_thickness DX/2] [--unpin]
+           [--wind WX WY WZ [--wind_drag 2] [--gust G HZ] [--gust_wave KX KY KZ]] [--air_drag C] [--vortex PX PY PZ NX NY NZ OMEGA RADIUS]...
+           [--blast CX CY CZ STRENGTH RADIUS T0 T1]... [--draw_colliders [--collider_color R G B]... [--checker S]
            [--shadows [--light X Y Z] [--shadow_strength 0.6] [--shadow_res 256]]]
            [--draw_points [--point_radius 1] [--point_color R G B] [--point_mode flat|strain|volume] [--point_range LO HI] [--point_xray]
            [--point_alpha 1] [--point_hidden_alpha 0] [--no_drag_marker]]
@@ -21,6 +23,9 @@ with --force / --drag, and images, --save_ply and --save_mesh follow the moving 
 --floor / --collide_sphere / --collide_inside give the object something to meet (Simulator.enable_contact): a floor at height Y, solid
 spheres (repeatable), a container sphere the object stays inside; --unpin clears every pin of the cloud, so the object can be dropped.  They compose with
 --force, --drag, --pin_*, --save_ply and --save_mesh.
+--wind / --air_drag / --vortex / --blast put force fields on the whole body (Simulator.enable_fields): a wind of velocity (WX, WY, WZ)
+that drags the object along at --wind_drag per second, gusting by --gust G HZ (and travelling through space with --gust_wave); still air that damps it
+at --air_drag per second; vortices (repeatable) and blasts with a time window (repeatable).  They compose with everything else.
 --draw_colliders draws those colliders into every frame (SimRenderHarness.draw_colliders): a shaded floor with a checker pattern of
 --checker world units (default 2 sim_dx; 0: none) and shaded spheres, depth-tested against the object; --collider_color (repeatable) colours them in slot order
 (the floor first, then the spheres, then the container).  It composes with --bg_radius, --force, --drag, --pin_*, --save_ply and --save_mesh.
@@ -110,6 +115,35 @@ def configure_contact(sim, args):
             ids.append(sim.add_sphere(args.collide_inside[:3], args.collide_inside[3], inside=True))
     except ValueError as e:   # a parameter out of range, a radius <= 0, a ninth collider
         raise SystemExit(f"contact: {e}")
+    return ids
+
+
+def wants_fields(args):
+    return args.wind is not None or args.air_drag is not None or bool(args.vortex) or bool(args.blast)
+
+
+def configure_fields(sim, args):
+    """--wind / --air_drag / --vortex / --blast as calls on `sim`, in that order; returns the fields' indices.  Nothing is called without one of them."""
+    if not wants_fields(args) or args.wind is None:
+        if any(v is not None for v in (args.wind_drag, args.gust, args.gust_wave)):
+            raise SystemExit("fields: --wind_drag / --gust / --gust_wave belong to --wind")
+        if not wants_fields(args):
+            return []
+    ids = []
+    try:
+        sim.enable_fields()
+        if args.wind is not None:
+            g, hz = args.gust if args.gust is not None else (0.0, 0.0)
+            ids.append(sim.add_wind(args.wind, drag=2.0 if args.wind_drag is None else args.wind_drag, gust=g, hz=hz,
+                                    wave=args.gust_wave if args.gust_wave is not None else (0.0, 0.0, 0.0)))
+        if args.air_drag is not None:
+            ids.append(sim.add_air_drag(args.air_drag))
+        for v in args.vortex or []:
+            ids.append(sim.add_vortex(v[0:3], v[3:6], v[6], v[7]))
+        for b in args.blast or []:
+            ids.append(sim.add_radial(b[0:3], b[3], b[4], start=b[5], stop=b[6]))
+    except ValueError as e:   # a value out of range, a zero axis, a ninth field
+        raise SystemExit(str(e) if str(e).startswith("fields: ") else f"fields: {e}")
     return ids
 
 
@@ -258,6 +292,7 @@ def run(args):
         except ValueError as e:   # a cloud without pinned points, a zero axis, a non-finite value
             raise SystemExit(f"--pin_shake / --pin_twist: {e}")
     configure_contact(h.sim, args)
+    configure_fields(h.sim, args)
     configure_overlay(h, args)
     configure_points(h, args)
     if args.save_mesh:
@@ -352,6 +387,15 @@ def parser():
     ap.add_argument("--friction", type=float, default=None, help="Coulomb friction coefficient of the colliders, >= 0 (default 0.5)")
     ap.add_argument("--contact_thickness", type=float, default=None, help="contact begins this far outside a collider (default: sim_dx / 2)")
     ap.add_argument("--unpin", action="store_true", help="clear every pin of the cloud: the object falls (give it a --floor)")
+    ap.add_argument("--wind", type=float, nargs=3, default=None, metavar=("WX", "WY", "WZ"), help="a wind of this velocity blows on the object (force fields, DESIGN.md 4.15)")
+    ap.add_argument("--wind_drag", type=float, default=None, metavar="C", help="how hard --wind drags the object along, 1/s, >= 0 (default 2)")
+    ap.add_argument("--gust", type=float, nargs=2, default=None, metavar=("G", "HZ"), help="--wind's velocity varies by 1 + G sin(2 pi HZ t), G in [0, 1]")
+    ap.add_argument("--gust_wave", type=float, nargs=3, default=None, metavar=("KX", "KY", "KZ"), help="the gust travels through space with this wave vector (cycles per unit)")
+    ap.add_argument("--air_drag", type=float, default=None, metavar="C", help="still air: mass-proportional damping of C per second, so a released object settles")
+    ap.add_argument("--vortex", type=float, nargs=8, action="append", default=None, metavar=("PX", "PY", "PZ", "NX", "NY", "NZ", "OMEGA", "RADIUS"),
+                    help="a vortex about the axis (NX, NY, NZ) through (PX, PY, PZ), OMEGA rad/s, nothing beyond RADIUS; repeatable")
+    ap.add_argument("--blast", type=float, nargs=7, action="append", default=None, metavar=("CX", "CY", "CZ", "STRENGTH", "RADIUS", "T0", "T1"),
+                    help="an acceleration of STRENGTH away from (CX, CY, CZ), nothing beyond RADIUS, while T0 <= t < T1 seconds; repeatable")
     ap.add_argument("--draw_colliders", action="store_true", help="draw the colliders into every frame (DESIGN.md 4.11); needs --floor, --collide_sphere or --collide_inside")
     ap.add_argument("--collider_color", type=float, nargs=3, action="append", default=None, metavar=("R", "G", "B"),
                     help="a collider's colour, in slot order; repeatable (default: a light grey for a plane, a mid grey otherwise)")
