@@ -713,6 +713,65 @@ int pn_sim_fields_rhs(int n_k, int n_IP, void* state, double dt, double dx, cons
                       const double* rho, const double* Nx, const int* kernel_bg, const int* kernel_cnt, const int* buffer, const double* Nx_csr,
                       const double* rhs_in, double* rhs_out, double* accel_out, void* stream);
 
+/* Self-contact (csrc/pn_selfcontact.hip; Simulator.enable_self_contact): the body collides with itself and with its own pieces.  A
+ * fifth right-hand-side stage, last in the chain rhs_gravity -> pins -> contact -> fields -> self: launches in front of every substep write
+ * rhs_out = rhs_in + the self-contact term of the state that substep starts from; the matrix, Ainv and the substep's kernels stay as they are.  All
+ * fp64.  x_i, v_i and m_i = rho[i] dx^3 as for contact (above); X_i is the point's rest position.  Parameters: kappa in (0, 1], beta in [0, 1],
+ * mu >= 0, the contact distance h > 0 (default dx: two cell centres touch a cell apart) and the exclusion radius rho_x >= h (default 3 h).
+ *   Eligible pairs: i != j with |X_i - X_j| >= rho_x (the squares summed as (q0 + q1) + q2, every operation rounded once).  Material adjacent at rest
+ * never repels itself, however compressed; two disconnected pieces are always eligible.  For an eligible pair
+ *     r = x_i - x_j,  L = |r|,  delta_ij = max(h - L, 0),  nh = r / L    (L = 0: nh = (0, 1, 0) for i < j, (0, -1, 0) for i > j: antisymmetric)
+ *     delta_ij = 0: the pair adds exactly nothing
+ *     S_i = sum_j delta_ij over the partners of i            w_ij = delta_ij / max(S_i, S_j)
+ * w_ij is symmetric, continuous when a partner enters at delta = 0, and sum_j w_ij delta_ij <= max_j delta_ij however many partners a crushed
+ * region gives a point.  With w = v_i - v_j, w_n = w.nh, w_t = w - w_n nh:
+ *     g = w_ij (kappa delta_ij + beta min(max(-w_n, 0) dt, delta_ij)) / dt^2,   g_t = min(mu g, w_ij |w_t| / dt)
+ *     a_i += (m_j / (m_i + m_j)) (g nh - g_t w_t / |w_t|)     (second term only when |w_t| > 0)
+ *     rhs_out[k 30 + j 3 + r] = rhs_in[...] + sum_e m_i Nx[i,slot,j] a_i[r]  over the (i, slot) entries e of kernel k's run, ascending.
+ * m_i a_i[from j] = -m_j a_j[from i]: the stage adds no net momentum.  A pair's relative response is at most (kappa + beta) delta_ij w_ij: contact's
+ * stability argument.  There is no continuous collision detection: a piece moving more than h per substep can tunnel (|v| dt < h).
+ *   Neighbour search, rebuilt on the device by every call.  A point's cell is floor(x / h) per axis in fp64, clamped to [-2^30, 2^30] as int32; a
+ * point whose x or v is not finite takes no part (S = 0, nobody's partner).  Bucket = ((uint32)cx 73856093 ^ (uint32)cy 19349663 ^
+ * (uint32)cz 83492791) & (T - 1), T the smallest power of two >= max(1024, 2 n_IP): hashed, so a falling or flying body needs no bounding box and no
+ * host read-back.  Table: count, exclusive scan, fill (integer atomics on counters and cursors), then every bucket in ascending point id, which makes
+ * the table independent of the atomics' order.  Point i visits the 27 cells c + (ox, oy, oz), oz outermost, each offset running -1, 0, 1; within a
+ * bucket ascending j; j is accepted only if j's own cell EQUALS the visited cell, so two cells hashed to one bucket never count a partner twice.
+ * Every floating-point sum (S_i, a_i) is taken in that order; none goes through an atomic.  Bounded cost: if any bucket holds more than
+ * PN_SELF_BUCKET_CAP points the call adds exactly nothing (rhs_out = rhs_in bit for bit) and `overflowed` grows by one: more than 64 points in one
+ * h^3 cell is a body that has already collapsed, and a blown-up run must not turn into an O(n^2) launch.  Layout of the state: */
+#define PN_SELF_BUCKET_CAP 64
+typedef struct pn_selfcontact_state {  /* 56 bytes = 7 doubles */
+    int active;          /* 0: rhs_out = rhs_in, bit for bit */
+    int reserved;
+    int64_t overflowed;  /* calls switched off because a bucket held more than PN_SELF_BUCKET_CAP points */
+    double kappa;        /* stiffness, in (0, 1] */
+    double beta;         /* damping, in [0, 1] */
+    double mu;           /* friction, >= 0 */
+    double h;            /* contact distance, > 0 */
+    double rho_x;        /* exclusion radius at rest, >= h */
+} pn_selfcontact_state;
+uint64_t pn_sim_self_bytes(void);        /* sizeof(pn_selfcontact_state) = 56 */
+/* Bytes of the work area for n_IP points: positions and velocities [n_IP,6], S [n_IP], a [n_IP,3] (fp64), cells and buckets [n_IP,4], the buckets'
+ * members twice [n_IP] (as placed, and sorted), and the table of T buckets: counts [T], starts [T + 1], two flag words.  0 for n_IP outside 1 .. 2^27. */
+uint64_t pn_sim_self_work_bytes(int n_IP);
+/* Kernel launches one pn_sim_self_rhs enqueues (8). */
+int pn_sim_self_launches(void);
+/* Writes `active` (0 or 1; -1 keeps it) and, with params5_host = (kappa, beta, mu, h, rho_x) != NULL, the parameters: finite, kappa in (0, 1], beta in
+ * [0, 1], mu >= 0, h > 0, rho_x >= h, else PN_ERR_ARG before anything is enqueued.  `overflowed` is left alone.  A one-thread launch on `stream`. */
+int pn_sim_self_set_params(void* state, int active, const double* params5_host, void* stream);
+/* rhs_out [10 n_k,3] = rhs_in + the self-contact term; rhs_in is left untouched and rhs_out is another buffer.  X_rest [n_IP,3]; the other tables are
+ * pn_sim_contact_rhs's; `work` has pn_sim_self_work_bytes(n_IP) bytes, 8-byte aligned, and may hold anything on entry.  accel_out [n_IP,3] = a_i
+ * (NULL: kept in the work area).  EIGHT ordinary launches on `stream`, none waiting for another workgroup: points and cells (the counts zeroed); count;
+ * scan and the overflow decision (one workgroup); fill; sort; S_i; a_i (a thread per point, one wave per workgroup); and the per-kernel sum in the
+ * order and with the reduction of pn_sim_contact_rhs's second launch (a workgroup of four waves per kernel, thread t taking the run's entries t,
+ * t + 256, ... ascending, shuffle tree 32 ... 1 per wave, then the waves in order through LDS, no atomics).  The same bits from every run on the same
+ * inputs.  A kernel none of whose points has a != 0, and every kernel when !active or the call overflowed, copies rhs_in bit for bit (-0.0 included).
+ * PN_ERR_ARG, before anything is enqueued, for a NULL pointer (accel_out excepted), rhs_in == rhs_out, dt or dx not > 0.  No allocation, no host
+ * synchronisation, capturable. */
+int pn_sim_self_rhs(int n_k, int n_IP, void* state, void* work, double dt, double dx, const double* dof, const double* dof_vel, const double* X_rest,
+                    const int* topo, const double* rho, const double* Nx, const int* kernel_bg, const int* kernel_cnt, const int* buffer,
+                    const double* Nx_csr, const double* rhs_in, double* rhs_out, double* accel_out, void* stream);
+
 /* The colliders drawn into a rendered frame (csrc/pn_colliders.hip; NeRFRenderer.set_collider_overlay): one launch behind the frame
  * driver, a thread per ray, composites the analytic surfaces of a pn_contact_state into `image` with a depth test against the object.  `contact_state`
  * is DEVICE memory with the pn_contact_state layout (the simulator's own buffer or a 744-byte copy), read at execution time: a captured launch follows

@@ -149,6 +149,11 @@ SIGNATURES = {
     "pn_sim_fields_set_field": (i32, [P, i32, i32, P, P]),
     "pn_sim_fields_clock": (i32, [P, C.c_int64, P]),
     "pn_sim_fields_rhs": (i32, [i32, i32, P, f64, f64, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "pn_sim_self_bytes": (u64, []),
+    "pn_sim_self_work_bytes": (u64, [i32]),
+    "pn_sim_self_launches": (i32, []),
+    "pn_sim_self_set_params": (i32, [P, i32, P, P]),
+    "pn_sim_self_rhs": (i32, [i32, i32, P, P, f64, f64, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "pn_draw_colliders": (i32, [P, C.POINTER(ColliderStyle), P, P, u32, f32, f32, f32, P, P, P, P, P, P]),
     "pn_draw_colliders_shadowed": (i32, [P, C.POINTER(ColliderStyle), P, P, u32, f32, f32, f32, P, P, P, P, P, ShadowLight, P, P, P, P]),
     "pn_points_keys_bytes": (u64, [i32, i32]),

@@ -49,6 +49,9 @@ UNITS = {
     "pn_pins.hip": ["-ffp-contract=fast"],   # fp64 sums in a fixed order: contraction does not touch the order, only the rounding of each step
     "pn_contact.hip": ["-ffp-contract=fast"],   # shares pn_sim_ip.h with pn_sim.hip (a point's position as update_F sums it); fp64 sums in a fixed order
     "pn_fields.hip": ["-ffp-contract=fast"],   # force fields: pn_sim_ip.h's point sums and contact's per-kernel sum restated, contracted as both are
+    # self-contact: pn_sim_ip.h's point sums and contact's per-kernel sum restated, contracted as both are; the one decision taken in floating point
+    # (a pair's eligibility at rest) switches contraction off for itself
+    "pn_selfcontact.hip": ["-ffp-contract=fast"],
     # the colliders drawn into a frame: per-ray fp32 with decisions in it (hit / miss, checker parity, in front of / behind the object), one rounding per
     # operation in source order, which tests/colliders_reference.py restates in numpy; a ray without a hit gets the frame epilogue's two roundings
     "pn_colliders.hip": ["-ffp-contract=off"],

@@ -199,6 +199,7 @@ class SimRenderHarness:
         self._graph_pins = self.sim.pin_enabled    # ... and so is its k_pin_rhs launch (Simulator.enable_pin_motion)
         self._graph_contact = self.sim.contact_enabled   # ... and its contact launches (Simulator.enable_contact)
         self._graph_fields = self.sim.fields_enabled     # ... and its force-field launches (Simulator.enable_fields)
+        self._graph_self = self.sim.self_contact_enabled   # ... and its self-contact launches (Simulator.enable_self_contact)
         self._graph_overlay = self.model.collider_overlay_key()   # ... and the render's collider overlay, with its style (draw_colliders)
         self._graph_points = self.model.point_overlay_key()   # ... and the point overlay's launch pair (draw_points)
         self._graph_form_epoch = self._net_form_epoch()
@@ -229,6 +230,11 @@ class SimRenderHarness:
         """Fields and the clock changed after a capture need no recapture (the state is device memory); the launches themselves must be in the graph."""
         if self.sim.fields_enabled and not captured:
             raise RuntimeError(f"fields: {what} was captured before enable_fields(), its substep ignores the force fields: {again} again")
+
+    def _check_self_captured(self, captured, what, again):
+        """Parameters changed after a capture need no recapture (the state is device memory); the launches themselves must be in the graph."""
+        if self.sim.self_contact_enabled and not captured:
+            raise RuntimeError(f"self-contact: {what} was captured before enable_self_contact(), its substep ignores self-contact: {again} again")
 
     def _check_overlay_captured(self, captured, what, again):
         """The colliders' state is device memory and is followed without a recapture; the overlay's launch, its style and t_max are in the graph."""
@@ -361,6 +367,7 @@ class SimRenderHarness:
         self._check_pins_captured(self._graph_pins, "the step graph", "capture()")
         self._check_contact_captured(self._graph_contact, "the step graph", "capture()")
         self._check_fields_captured(getattr(self, "_graph_fields", False), "the step graph", "capture()")
+        self._check_self_captured(getattr(self, "_graph_self", False), "the step graph", "capture()")
         self._check_overlay_captured(self._graph_overlay, "the step graph", "capture()")
         self._check_points_captured(getattr(self, "_graph_points", None), "the step graph", "capture()")
         self._check_previous_graph_frame()
@@ -477,6 +484,7 @@ class SimRenderHarness:
         self._pipe_pins = self.sim.pin_enabled
         self._pipe_contact = self.sim.contact_enabled
         self._pipe_fields = self.sim.fields_enabled
+        self._pipe_self = self.sim.self_contact_enabled
         self._pipe_overlay = self.model.collider_overlay_key()
         self._pipe_points = self.model.point_overlay_key()
         self._pipe_single = not frame_parallel and not (render_kw or {}).get("ray_batch")
@@ -496,6 +504,7 @@ class SimRenderHarness:
         self._check_pins_captured(self._pipe_pins, "the pipeline", "capture_pipelined()")
         self._check_contact_captured(self._pipe_contact, "the pipeline", "capture_pipelined()")
         self._check_fields_captured(getattr(self, "_pipe_fields", False), "the pipeline", "capture_pipelined()")
+        self._check_self_captured(getattr(self, "_pipe_self", False), "the pipeline", "capture_pipelined()")
         if not getattr(self, "_pipe_single", True):
             self._refuse_overlay_form("the frame-parallel / staged pipeline")
             self._refuse_points_form("the frame-parallel / staged pipeline")

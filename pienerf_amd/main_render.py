@@ -7,7 +7,9 @@ deformed point cloud and the per-frame IP state the reference's ``main_render.py
            [--floor Y] [--collide_sphere CX CY CZ R]... [--collide_inside CX CY CZ R] [--contact_stiffness 0.5 --contact_damping 0.5 --friction 0.5
            --contact_thickness DX/2] [--unpin]
            [--wind WX WY WZ [--wind_drag 2] [--gust G HZ] [--gust_wave KX KY KZ]] [--air_drag C] [--vortex PX PY PZ NX NY NZ OMEGA RADIUS]...
-           [--blast CX CY CZ STRENGTH RADIUS T0 T1]... [--draw_colliders [--collider_color R G B]... [--checker S]
+           [--blast CX CY CZ STRENGTH RADIUS T0 T1]...
+           [--self_contact [--self_thickness H] [--self_exclusion R] [--self_stiffness 0.5] [--self_damping 0.5] [--self_friction 0]]
+           [--draw_colliders [--collider_color R G B]... [--checker S]
            [--shadows [--light X Y Z] [--shadow_strength 0.6] [--shadow_res 256]]]
            [--draw_points [--point_radius 1] [--point_color R G B] [--point_mode flat|strain|volume] [--point_range LO HI] [--point_xray]
            [--point_alpha 1] [--point_hidden_alpha 0] [--no_drag_marker]]
@@ -26,6 +28,9 @@ spheres (repeatable), a container sphere the object stays inside; --unpin clears
 --wind / --air_drag / --vortex / --blast put force fields on the whole body (Simulator.enable_fields): a wind of velocity (WX, WY, WZ)
 that drags the object along at --wind_drag per second, gusting by --gust G HZ (and travelling through space with --gust_wave); still air that damps it
 at --air_drag per second; vortices (repeatable) and blasts with a time window (repeatable).  They compose with everything else.
+--self_contact keeps the body out of itself and lets the separate pieces of one cloud collide (Simulator.enable_self_contact): integration
+points closer than --self_thickness (default sim_dx) that were at least --self_exclusion apart at rest (default 3 x the thickness) repel each other.  It
+composes with every other flag.
 --draw_colliders draws those colliders into every frame (SimRenderHarness.draw_colliders): a shaded floor with a checker pattern of
 --checker world units (default 2 sim_dx; 0: none) and shaded spheres, depth-tested against the object; --collider_color (repeatable) colours them in slot order
 (the floor first, then the spheres, then the container).  It composes with --bg_radius, --force, --drag, --pin_*, --save_ply and --save_mesh.
@@ -145,6 +150,27 @@ def configure_fields(sim, args):
     except ValueError as e:   # a value out of range, a zero axis, a ninth field
         raise SystemExit(str(e) if str(e).startswith("fields: ") else f"fields: {e}")
     return ids
+
+
+def check_self_contact_args(args):
+    """What configure_self_contact refuses, before anything is built."""
+    opts = (args.self_thickness, args.self_exclusion, args.self_stiffness, args.self_damping, args.self_friction)
+    if not args.self_contact and any(v is not None for v in opts):
+        raise SystemExit("--self_thickness / --self_exclusion / --self_stiffness / --self_damping / --self_friction need --self_contact")
+
+
+def configure_self_contact(sim, args):
+    """--self_contact and its options as one call on `sim`; nothing is called without the flag."""
+    check_self_contact_args(args)
+    if not args.self_contact:
+        return False
+    d = lambda v, dflt: dflt if v is None else v
+    try:
+        sim.enable_self_contact(stiffness=d(args.self_stiffness, 0.5), damping=d(args.self_damping, 0.5), friction=d(args.self_friction, 0.0),
+                                thickness=args.self_thickness, exclusion=args.self_exclusion)
+    except ValueError as e:   # a value out of range
+        raise SystemExit(str(e))
+    return True
 
 
 def configure_overlay(h, args):
@@ -272,6 +298,7 @@ def run(args):
     if args.pin_centre is not None and args.pin_twist is None:
         raise SystemExit("--pin_centre is the centre of --pin_twist")
     check_overlay_args(args)
+    check_self_contact_args(args)
     h = build_harness(args)
     pose = scene.orbit_pose(args.radius, args.azimuth, args.elevation)
     os.makedirs(args.out, exist_ok=True)
@@ -293,6 +320,7 @@ def run(args):
             raise SystemExit(f"--pin_shake / --pin_twist: {e}")
     configure_contact(h.sim, args)
     configure_fields(h.sim, args)
+    configure_self_contact(h.sim, args)
     configure_overlay(h, args)
     configure_points(h, args)
     if args.save_mesh:
@@ -340,6 +368,9 @@ def run(args):
             print(f"video: {args.frames} frames, {video.bytes} bytes of JPEG -> {os.path.abspath(video.path)}")
     if h.sim.contact_enabled and not args.quiet:
         print(f"contact: {h.sim.contact_count()} of {h.sim.n_IP} integration points in contact in the last substep")
+    if h.sim.self_contact_enabled and not args.quiet:
+        print(f"self-contact: {h.sim.self_contact_count()} of {h.sim.n_IP} integration points in contact with the body itself in the last substep, "
+              f"{h.sim.self_contact_overflows()} substeps over the bucket cap")
     if not args.quiet:
         print(f"{args.frames} frames -> {os.path.abspath(args.out)} in {time.time() - t0:.2f} s; last frame: {h.model.last_stats}")
     return written
@@ -396,6 +427,12 @@ def parser():
                     help="a vortex about the axis (NX, NY, NZ) through (PX, PY, PZ), OMEGA rad/s, nothing beyond RADIUS; repeatable")
     ap.add_argument("--blast", type=float, nargs=7, action="append", default=None, metavar=("CX", "CY", "CZ", "STRENGTH", "RADIUS", "T0", "T1"),
                     help="an acceleration of STRENGTH away from (CX, CY, CZ), nothing beyond RADIUS, while T0 <= t < T1 seconds; repeatable")
+    ap.add_argument("--self_contact", action="store_true", help="the body collides with itself and with its own pieces (DESIGN.md 4.16)")
+    ap.add_argument("--self_thickness", type=float, default=None, metavar="H", help="two integration points touch at this distance, > 0 (default: sim_dx)")
+    ap.add_argument("--self_exclusion", type=float, default=None, metavar="R", help="points closer than this at rest never repel each other (default: 3 H)")
+    ap.add_argument("--self_stiffness", type=float, default=None, metavar="K", help="share of an overlap removed per substep, in (0, 1] (default 0.5)")
+    ap.add_argument("--self_damping", type=float, default=None, metavar="B", help="share of the approach velocity removed per substep, in [0, 1] (default 0.5)")
+    ap.add_argument("--self_friction", type=float, default=None, metavar="MU", help="friction between the touching parts, >= 0 (default 0)")
     ap.add_argument("--draw_colliders", action="store_true", help="draw the colliders into every frame (DESIGN.md 4.11); needs --floor, --collide_sphere or --collide_inside")
     ap.add_argument("--collider_color", type=float, nargs=3, action="append", default=None, metavar=("R", "G", "B"),
                     help="a collider's colour, in slot order; repeatable (default: a light grey for a plane, a mid grey otherwise)")

@@ -68,6 +68,23 @@ def make_chair_points(sub_res=60, bound=1.0, lam=1e6, mu=1e6, density=1e3, pin_h
                 pin=(pts[:, 1] < ymin + pin_height).astype(np.int32))
 
 
+def make_block_points(lo, hi, sub_res=60, bound=1.0, lam=1e6, mu=1e6, density=1e3, pinned=False, hgs=0.06):
+    """A solid box [lo, hi] sampled as make_chair_points samples the chair, with the same dict; pinned: every point of it, or none.  A cloud of several
+    pieces is the pieces' arrays concatenated (concat_clouds)."""
+    lo, hi = np.asarray(lo, np.float64).reshape(3), np.asarray(hi, np.float64).reshape(3)
+    box = np.array([[lo[0], hi[0], lo[1], hi[1], lo[2], hi[2]]])
+    c = make_chair_points(sub_res=sub_res, bound=bound, lam=lam, mu=mu, density=density, pin_height=0.0, boxes=box, hgs=hgs)
+    if len(c["pos"]) == 0:
+        raise ValueError(f"make_block_points: no lattice point of sub_res={sub_res} lies inside {lo.tolist()} .. {hi.tolist()}")
+    c["pin"] = np.full(len(c["pos"]), int(bool(pinned)), np.int32)
+    return c
+
+
+def concat_clouds(*clouds):
+    """One cloud holding the pieces' points one after the other."""
+    return {k: np.concatenate([c[k] for c in clouds]) for k in clouds[0]}
+
+
 # ------------------------------------------------------------------ PLY
 _PLY_PROPS = [("x", "f8"), ("y", "f8"), ("z", "f8"), ("mass", "f8"), ("mu", "f8"), ("lam", "f8"), ("pin", "i4")]
 _PLY_TYPES = {"f8": "double", "f4": "float", "i4": "int", "u1": "uchar", "i2": "short", "u2": "ushort", "u4": "uint", "i1": "char"}
