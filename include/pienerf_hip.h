@@ -648,14 +648,22 @@ int pn_sim_contact_set_collider(void* state, int index, int type, const double* 
 /* rhs_out [10 n_k,3] = rhs_in + the contact term; rhs_in is left untouched and rhs_out is another buffer.  topo [n_IP,8], rho [n_IP], Nx [n_IP,8,10];
  * kernel_bg / kernel_cnt [n_k] and buffer [8 n_IP] (entry = point 8 + slot) the per-kernel CSR of pn_sim_stepforward, Nx_csr [8 n_IP,10] the Nx rows in
  * that order.  With accel_out [n_IP,3]: TWO launches, the measured faster form — a thread per point writes accel_out = a_i (zeros for a
- * point not in contact), then a workgroup of four waves per kernel, thread t taking the run's entries t, t + 256, ... in ascending order, adds
- * m_i Nx a_i: shuffle tree per wave, then the waves in order through LDS.  accel_out NULL: ONE launch, the same workgroups with every entry evaluating
+ * point not in contact), then the per-kernel sum of pn_sim_accel_rhs (below) adds m_i Nx a_i.  accel_out NULL: ONE launch, the same workgroups with every entry evaluating
  * its point itself (8 x redundant across a point's kernels; every workgroup runs the same code on the same inputs, so all agree on a point to the
  * bit) — the same bits in rhs_out.  No atomics: the order of every sum is a function of the kernel's run alone.  A kernel none of whose points
  * is in contact, and every kernel when !active or n == 0, copies rhs_in bit for bit.  No allocation, no host synchronisation, capturable. */
 int pn_sim_contact_rhs(int n_k, int n_IP, const void* state, double dt, double dx, const double* dof, const double* dof_vel, const int* topo,
                        const double* rho, const double* Nx, const int* kernel_bg, const int* kernel_cnt, const int* buffer, const double* Nx_csr,
                        const double* rhs_in, double* rhs_out, double* accel_out, void* stream);
+/* The per-kernel sum that contact, the force fields and self-contact share (csrc/pn_sim_rhs.h: pn_kernel_accel_term), on its own: ONE launch,
+ *     rhs_out[k 30 + j 3 + r] = rhs_in[...] + sum_e rho[i] dx^3 Nx_csr[e,j] accel[i,r]   over the entries e of kernel k's run, i = buffer[e] >> 3,
+ * a workgroup of four waves per kernel, thread t taking the run's entries t, t + 256, ... in ascending order (an entry whose point has accel = 0 is
+ * skipped), shuffle tree 32 ... 1 per wave, then the waves in the order ((w0 + w1) + w2) + w3 through LDS, no atomics.  A kernel none of whose points
+ * has accel != 0 copies rhs_in bit for bit (-0.0 included).  This is the last launch of pn_sim_contact_rhs, pn_sim_fields_rhs and pn_sim_self_rhs with
+ * their stage switched on: called on a stage's accel_out and rhs_in it returns that stage's rhs_out to the bit.  PN_ERR_ARG, before anything is
+ * enqueued, for a NULL pointer, rhs_in == rhs_out, dx not finite and > 0, n_IP outside 1 .. 2^27.  No allocation, no host synchronisation, capturable. */
+int pn_sim_accel_rhs(int n_k, int n_IP, double dx, const double* rho, const int* kernel_bg, const int* kernel_cnt, const int* buffer,
+                     const double* Nx_csr, const double* accel, const double* rhs_in, double* rhs_out, void* stream);
 
 /* Force fields (csrc/pn_fields.hip; Simulator.enable_fields): wind, vortex and blast on the whole body, with air drag.  A fourth
  * right-hand-side stage beside drag, pins and contact: launches in front of every substep write rhs_out = rhs_in + the field term of the state and the
@@ -703,9 +711,8 @@ int pn_sim_fields_set_field(void* state, int index, int type, const double* geom
 /* k = the clock's new value (>= 0), by a one-thread launch on `stream`. */
 int pn_sim_fields_clock(void* state, int64_t k, void* stream);
 /* rhs_out [10 n_k,3] = rhs_in + the field term at t = k dt, then k += 1; rhs_in is left untouched and rhs_out is another buffer.  The tables are
- * pn_sim_contact_rhs's.  THREE launches: a thread per point writes accel_out [n_IP,3] = a_i (one wave per workgroup); a workgroup of four waves per
- * kernel, thread t taking the run's entries t, t + 256, ... in ascending order, adds m_i Nx a_i: shuffle tree 32 ... 1 per wave, then the waves in
- * order through LDS, no atomics — the order and the reduction of pn_sim_contact_rhs's second launch; and a one-thread launch BEHIND them advances the
+ * pn_sim_contact_rhs's.  THREE launches: a thread per point writes accel_out [n_IP,3] = a_i (one wave per workgroup); the per-kernel sum of
+ * pn_sim_accel_rhs (above) adds m_i Nx a_i, no atomics; and a one-thread launch BEHIND them advances the
  * clock (no workgroup reads a clock that its own launch advances).  A kernel none of whose points has a != 0, and every kernel when !active, n == 0 or
  * t is outside every window, copies rhs_in bit for bit (-0.0 included).  PN_ERR_ARG for a NULL pointer, rhs_in == rhs_out, dt or dx not > 0.  No
  * allocation, no host synchronisation, capturable. */
@@ -762,9 +769,8 @@ int pn_sim_self_set_params(void* state, int active, const double* params5_host, 
 /* rhs_out [10 n_k,3] = rhs_in + the self-contact term; rhs_in is left untouched and rhs_out is another buffer.  X_rest [n_IP,3]; the other tables are
  * pn_sim_contact_rhs's; `work` has pn_sim_self_work_bytes(n_IP) bytes, 8-byte aligned, and may hold anything on entry.  accel_out [n_IP,3] = a_i
  * (NULL: kept in the work area).  EIGHT ordinary launches on `stream`, none waiting for another workgroup: points and cells (the counts zeroed); count;
- * scan and the overflow decision (one workgroup); fill; sort; S_i; a_i (a thread per point, one wave per workgroup); and the per-kernel sum in the
- * order and with the reduction of pn_sim_contact_rhs's second launch (a workgroup of four waves per kernel, thread t taking the run's entries t,
- * t + 256, ... ascending, shuffle tree 32 ... 1 per wave, then the waves in order through LDS, no atomics).  The same bits from every run on the same
+ * scan and the overflow decision (one workgroup); fill; sort; S_i; a_i (a thread per point, one wave per workgroup); and the per-kernel sum of
+ * pn_sim_accel_rhs (above), no atomics.  The same bits from every run on the same
  * inputs.  A kernel none of whose points has a != 0, and every kernel when !active or the call overflowed, copies rhs_in bit for bit (-0.0 included).
  * PN_ERR_ARG, before anything is enqueued, for a NULL pointer (accel_out excepted), rhs_in == rhs_out, dt or dx not > 0.  No allocation, no host
  * synchronisation, capturable. */

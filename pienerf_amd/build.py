@@ -47,10 +47,11 @@ UNITS = {
     "pn_sim.hip": ["-ffp-contract=fast"],
     "pn_drag.hip": ["-ffp-contract=fast"],   # shares pn_sim_ip.h with pn_sim.hip: the same contraction, the same bits
     "pn_pins.hip": ["-ffp-contract=fast"],   # fp64 sums in a fixed order: contraction does not touch the order, only the rounding of each step
-    "pn_contact.hip": ["-ffp-contract=fast"],   # shares pn_sim_ip.h with pn_sim.hip (a point's position as update_F sums it); fp64 sums in a fixed order
-    "pn_fields.hip": ["-ffp-contract=fast"],   # force fields: pn_sim_ip.h's point sums and contact's per-kernel sum restated, contracted as both are
-    # self-contact: pn_sim_ip.h's point sums and contact's per-kernel sum restated, contracted as both are; the one decision taken in floating point
-    # (a pair's eligibility at rest) switches contraction off for itself
+    # contact, force fields, self-contact: one source for a point's state and for the per-kernel sum (pn_sim_rhs.h, on top of pn_sim_ip.h, which
+    # pn_sim.hip shares: a point's position as update_F sums it), so the three contract alike and the bits agree; fp64 sums in a fixed order
+    "pn_contact.hip": ["-ffp-contract=fast"],
+    "pn_fields.hip": ["-ffp-contract=fast"],
+    # the one decision self-contact takes in floating point (a pair's eligibility at rest) switches contraction off for itself
     "pn_selfcontact.hip": ["-ffp-contract=fast"],
     # the colliders drawn into a frame: per-ray fp32 with decisions in it (hit / miss, checker parity, in front of / behind the object), one rounding per
     # operation in source order, which tests/colliders_reference.py restates in numpy; a ray without a hit gets the frame epilogue's two roundings

@@ -9,14 +9,13 @@
 #include <math.h>
 
 #include "pn_common.h"
-#include "pn_sim_ip.h"
+#include "pn_sim_rhs.h"
 
-static_assert(sizeof(pn_contact_collider) == 88, "pn_contact_collider: 88 bytes (pienerf_amd/simulator/solver.py: CONTACT_COLLIDER_DTYPE)");
-static_assert(sizeof(pn_contact_state) == 744, "pn_contact_state: 744 bytes (pienerf_amd/simulator/solver.py allocates it as 93 doubles)");
+static_assert(sizeof(pn_contact_collider) == 88, "pn_contact_collider: 88 bytes (pienerf_amd/simulator/contact.py: CONTACT_COLLIDER_DTYPE)");
+static_assert(sizeof(pn_contact_state) == 744, "pn_contact_state: 744 bytes (pienerf_amd/simulator/contact.py: CONTACT_STATE_DTYPE)");
 static_assert(PN_CONTACT_SLOTS == 8, "pn_contact_state: 8 collider slots");
 
 #define PN_CONTACT_THREADS 256   // four waves per GMLS kernel; fixed: the order of the sum must not depend on the device
-#define PN_CONTACT_WAVES (PN_CONTACT_THREADS / 64)
 
 // ------------------------------------------------------------------------------------------------ the law, per integration point
 // a += a_n n - a_t w_t / |w_t| over the colliders 0 .. n-1 in index order; returns whether any collider is penetrated (delta > 0).  A collider with
@@ -64,19 +63,12 @@ __device__ __forceinline__ bool pn_contact_law(const pn_contact_state* __restric
     return hit;
 }
 
-// A point's position and velocity (pn_ip_row_acc over its 8 kernels, slots 0..7 one after the other, fp64, not rounded to fp32), then the law.  Returns
-// whether the point is in contact; a = 0 when it is not.
+// A point's position and velocity (pn_ip_state), then the law.  Returns whether the point is in contact; a = 0 when it is not.
 __device__ __forceinline__ bool pn_contact_point(int p, int n_k, const pn_contact_state* __restrict__ st, int n, double dt, const double* __restrict__ dof,
                                                  const double* __restrict__ dof_vel, const int* __restrict__ topo, const double* __restrict__ Nx, double a[3]) {
-    double x[3] = {0.0, 0.0, 0.0}, v[3] = {0.0, 0.0, 0.0};
+    double x[3], v[3];
     a[0] = a[1] = a[2] = 0.0;
-    for (int i = 0; i < 8; i++) {
-        const int k = topo[p * 8 + i];
-        if ((unsigned)k >= (unsigned)n_k) return false;  // never with the tables solver.py builds; keeps every read inside its buffer
-        const double* S = Nx + ((size_t)p * 8 + i) * 10;
-        pn_ip_row_acc(dof + (size_t)k * 30, S, x[0], x[1], x[2]);
-        pn_ip_row_acc(dof_vel + (size_t)k * 30, S, v[0], v[1], v[2]);
-    }
+    if (!pn_ip_state(p, n_k, dof, dof_vel, topo, Nx, x, v)) return false;
     if (pn_contact_law(st, n, dt, x, v, a)) return true;
     a[0] = a[1] = a[2] = 0.0;
     return false;
@@ -98,13 +90,10 @@ __global__ void __launch_bounds__(PN_CONTACT_POINT_THREADS) k_contact_points(int
 }
 
 // ------------------------------------------------------------------------------------------------ the right-hand side, every substep
-// One workgroup of four waves per GMLS kernel.  Thread t takes the entries t, t + 256, ... of the kernel's run (kernel_bg / kernel_cnt / buffer: the
-// (point, slot) pairs, ascending) in ascending order and adds m Nx[point, slot, j] a[r] into 30 sums, a = the point's contact acceleration: read from
-// `accel` (written by k_contact_points in the launch before this one), or with FUSED evaluated here by the same pn_contact_point — 8 x redundant across
-// a point's kernels, but one launch; every workgroup that evaluates a point runs the same code on the same inputs, so all agree on it to the bit.
-// Each wave adds its lanes by the shuffle tree 32, 16 ... 1, lane 0 of each wave puts its totals into LDS, and the 30 threads that write add the
-// waves in the order ((w0 + w1) + w2) + w3.  No atomics; the order is a function of the run alone.  A kernel none of whose points has a != 0, and so
-// every kernel of an inactive or empty state, copies rhs_in's bits (g + 0.0 would turn a -0.0 into +0.0).
+// rhs_out = rhs_in + the contact term: pn_kernel_accel_term (pn_sim_rhs.h), one workgroup of four waves per GMLS kernel.  a = the point's contact
+// acceleration: read from `accel` (written by k_contact_points in the launch before this one), or with FUSED evaluated here by the same
+// pn_contact_point — 8 x redundant across a point's kernels, but one launch; every workgroup that evaluates a point runs the same code on the same
+// inputs, so all agree on it to the bit.  A point not in contact has a = 0 (a penetrated collider always pushes: a_n > 0).
 template <bool FUSED>
 __global__ void __launch_bounds__(PN_CONTACT_THREADS) k_contact_rhs(int n_k, int n_IP, const pn_contact_state* __restrict__ st, double dt, double dx3,
                                                                     const double* __restrict__ dof, const double* __restrict__ dof_vel,
@@ -113,63 +102,34 @@ __global__ void __launch_bounds__(PN_CONTACT_THREADS) k_contact_rhs(int n_k, int
                                                                     const int* __restrict__ kernel_cnt, const int* __restrict__ buffer,
                                                                     const double* __restrict__ Nx_csr, const double* __restrict__ rhs_in,
                                                                     double* __restrict__ rhs_out, const double* __restrict__ accel) {
-    __shared__ double s_part[PN_CONTACT_WAVES][30];
-    const int kid = blockIdx.x, t = threadIdx.x;
-    const int bg = min(max(kernel_bg[kid], 0), 8 * n_IP), end = min(bg + max(kernel_cnt[kid], 0), 8 * n_IP);
-    const double* g = rhs_in + (size_t)kid * 30;
-    double* o = rhs_out + (size_t)kid * 30;
-    int n = 0;
-    bool on = true;
     if (FUSED) {
-        n = min(st->n, PN_CONTACT_SLOTS);
-        on = st->active != 0 && n > 0;  // uniform over the launch
+        const int n = min(st->n, PN_CONTACT_SLOTS);
+        const bool on = st->active != 0 && n > 0;  // uniform over the launch
+        pn_kernel_accel_term<PN_CONTACT_THREADS>(blockIdx.x, threadIdx.x, on, n_IP, dx3, rho, kernel_bg, kernel_cnt, buffer, Nx_csr, rhs_in, rhs_out,
+                                                 [&](int p, double a[3]) { pn_contact_point(p, n_k, st, n, dt, dof, dof_vel, topo, Nx, a); });
+    } else {
+        pn_kernel_accel_term<PN_CONTACT_THREADS>(blockIdx.x, threadIdx.x, true, n_IP, dx3, rho, kernel_bg, kernel_cnt, buffer, Nx_csr, rhs_in, rhs_out,
+                                                 PnAccelRead{accel});
     }
-    double acc[30];
-#pragma unroll
-    for (int i = 0; i < 30; i++) acc[i] = 0.0;
-    int hit = 0;
-    if (on) {
-        for (int e = bg + t; e < end; e += PN_CONTACT_THREADS) {
-            const int p = buffer[e] >> 3;
-            if ((unsigned)p >= (unsigned)n_IP) continue;  // never with the tables solver.py builds; keeps every read inside its buffer
-            double a[3];
-            if (FUSED) {
-                pn_contact_point(p, n_k, st, n, dt, dof, dof_vel, topo, Nx, a);
-            } else {
-                a[0] = accel[(size_t)p * 3]; a[1] = accel[(size_t)p * 3 + 1]; a[2] = accel[(size_t)p * 3 + 2];
-            }
-            if (a[0] == 0.0 && a[1] == 0.0 && a[2] == 0.0) continue;  // not in contact (a penetrated collider always pushes: a_n > 0)
-            hit = 1;
-            const double m = rho[p] * dx3;
-            const double* N = Nx_csr + (size_t)e * 10;
-#pragma unroll
-            for (int b = 0; b < 10; b++) {
-                const double w = m * N[b];
-#pragma unroll
-                for (int c = 0; c < 3; c++) acc[b * 3 + c] += w * a[c];
-            }
-        }
-    }
-    if (!__syncthreads_or(hit)) {  // uniform over the workgroup
-        if (t < 30) o[t] = g[t];
-        return;
-    }
-#pragma unroll
-    for (int i = 0; i < 30; i++) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) acc[i] += __shfl_down(acc[i], off);
-    }
-    if ((t & 63) == 0) {
-#pragma unroll
-        for (int i = 0; i < 30; i++) s_part[t >> 6][i] = acc[i];
-    }
-    __syncthreads();
-    if (t < 30) {
-        double s = s_part[0][t];
-#pragma unroll
-        for (int w = 1; w < PN_CONTACT_WAVES; w++) s += s_part[w][t];
-        o[t] = g[t] + s;
-    }
+}
+
+// the shared sum on its own, `accel` as given: what the three stages' last launches compute (tests/test_gpu_rhs_term.py)
+__global__ void __launch_bounds__(PN_CONTACT_THREADS) k_accel_rhs(int n_IP, double dx3, const double* __restrict__ rho, const int* __restrict__ kernel_bg,
+                                                                  const int* __restrict__ kernel_cnt, const int* __restrict__ buffer,
+                                                                  const double* __restrict__ Nx_csr, const double* __restrict__ rhs_in,
+                                                                  double* __restrict__ rhs_out, const double* __restrict__ accel) {
+    pn_kernel_accel_term<PN_CONTACT_THREADS>(blockIdx.x, threadIdx.x, true, n_IP, dx3, rho, kernel_bg, kernel_cnt, buffer, Nx_csr, rhs_in, rhs_out,
+                                             PnAccelRead{accel});
+}
+
+extern "C" int pn_sim_accel_rhs(int n_k, int n_IP, double dx, const double* rho, const int* kernel_bg, const int* kernel_cnt, const int* buffer,
+                                const double* Nx_csr, const double* accel, const double* rhs_in, double* rhs_out, void* stream) {
+    PN_REQUIRE(n_k > 0 && n_IP > 0 && n_IP <= (1 << 27) && rho && kernel_bg && kernel_cnt && buffer && Nx_csr && accel);
+    PN_REQUIRE(rhs_in && rhs_out && rhs_in != rhs_out);
+    PN_REQUIRE(isfinite(dx) && dx > 0.0);
+    k_accel_rhs<<<n_k, PN_CONTACT_THREADS, 0, (hipStream_t)stream>>>(n_IP, pow(dx, 3.0), rho, kernel_bg, kernel_cnt, buffer, Nx_csr, rhs_in, rhs_out, accel);
+    PN_LAUNCH_CHECK();
+    return PN_OK;
 }
 
 extern "C" uint64_t pn_sim_contact_bytes(void) { return sizeof(pn_contact_state); }

@@ -10,7 +10,7 @@
 #include "pn_common.h"
 #include "pn_sim_ip.h"
 
-static_assert(sizeof(pn_drag_state) == 40, "pn_drag_state: 40 bytes (pienerf_amd/simulator/solver.py allocates it as 5 doubles)");
+static_assert(sizeof(pn_drag_state) == 40, "pn_drag_state: 40 bytes (pienerf_amd/simulator/drag.py allocates it as 5 doubles)");
 
 #define PN_DRAG_BLOCKS 128       // workgroups of the zero-depth fallback's first pass (fixed: the sum's order must not depend on the device)
 #define PN_DRAG_THREADS 256

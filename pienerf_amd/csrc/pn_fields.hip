@@ -9,14 +9,13 @@
 #include <math.h>
 
 #include "pn_common.h"
-#include "pn_sim_ip.h"
+#include "pn_sim_rhs.h"
 
-static_assert(sizeof(pn_force_field) == 144, "pn_force_field: 144 bytes (pienerf_amd/simulator/solver.py: FIELD_DTYPE)");
-static_assert(sizeof(pn_field_state) == 1168, "pn_field_state: 1168 bytes (pienerf_amd/simulator/solver.py allocates it as 146 doubles)");
+static_assert(sizeof(pn_force_field) == 144, "pn_force_field: 144 bytes (pienerf_amd/simulator/fields.py: FIELD_DTYPE)");
+static_assert(sizeof(pn_field_state) == 1168, "pn_field_state: 1168 bytes (pienerf_amd/simulator/fields.py: FIELD_STATE_DTYPE)");
 static_assert(PN_FIELD_SLOTS == 8, "pn_field_state: 8 field slots");
 
 #define PN_FIELD_THREADS 256   // four waves per GMLS kernel; fixed: the order of the sum must not depend on the device
-#define PN_FIELD_WAVES (PN_FIELD_THREADS / 64)
 #define PN_FIELD_2PI 6.283185307179586476925286766559
 
 // ------------------------------------------------------------------------------------------------ the law, per integration point
@@ -65,8 +64,8 @@ __device__ __forceinline__ void pn_field_law(const pn_field_state* __restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------------ the law at every point (first of three launches)
-// One thread per integration point: its position and velocity as pn_contact_point sums them (pn_ip_row_acc over its 8 kernels, slots 0..7 one after
-// the other, fp64), then the law at t = k dt: accel[p] = a_p, zeros for every point of an inactive or empty state.
+// One thread per integration point: its position and velocity (pn_ip_state), then the law at t = k dt: accel[p] = a_p, zeros for every point of an
+// inactive or empty state.
 #define PN_FIELD_POINT_THREADS 64   // 3 576 points on the chair: 56 workgroups of one wave, spread over the CUs
 __global__ void __launch_bounds__(PN_FIELD_POINT_THREADS) k_field_points(int n_k, int n_IP, const pn_field_state* __restrict__ st, double dt,
                                                                          const double* __restrict__ dof, const double* __restrict__ dof_vel,
@@ -77,82 +76,23 @@ __global__ void __launch_bounds__(PN_FIELD_POINT_THREADS) k_field_points(int n_k
     const int n = min(max(st->n, 0), PN_FIELD_SLOTS);
     double a[3] = {0.0, 0.0, 0.0};
     if (st->active != 0 && n > 0) {
-        double x[3] = {0.0, 0.0, 0.0}, v[3] = {0.0, 0.0, 0.0};
-        bool ok = true;
-        for (int i = 0; i < 8; i++) {
-            const int k = topo[p * 8 + i];
-            if ((unsigned)k >= (unsigned)n_k) {  // never with the tables solver.py builds; keeps every read inside its buffer
-                ok = false;
-                break;
-            }
-            const double* S = Nx + ((size_t)p * 8 + i) * 10;
-            pn_ip_row_acc(dof + (size_t)k * 30, S, x[0], x[1], x[2]);
-            pn_ip_row_acc(dof_vel + (size_t)k * 30, S, v[0], v[1], v[2]);
-        }
-        if (ok) pn_field_law(st, n, (double)st->k * dt, dt, x, v, a);
+        double x[3], v[3];
+        if (pn_ip_state(p, n_k, dof, dof_vel, topo, Nx, x, v)) pn_field_law(st, n, (double)st->k * dt, dt, x, v, a);
     }
     accel[(size_t)p * 3] = a[0]; accel[(size_t)p * 3 + 1] = a[1]; accel[(size_t)p * 3 + 2] = a[2];
 }
 
 // ------------------------------------------------------------------------------------------------ the right-hand side, every substep
-// One workgroup of four waves per GMLS kernel, in the order and with the reduction of k_contact_rhs<false> (restated here, so that contact's code and
-// bits stay as they are): thread t takes the entries t, t + 256, ... of the kernel's run in ascending order and adds m Nx[point, slot, j] a[r] into 30
-// sums, a read from `accel` (written by k_field_points in the launch before this one).  Each wave adds its lanes by the shuffle tree 32, 16 ... 1,
-// lane 0 of each wave puts its totals into LDS, and the 30 threads that write add the waves in the order ((w0 + w1) + w2) + w3.  No atomics.  A
-// kernel none of whose points has a != 0, and so every kernel of a state that is inactive, empty or outside all its windows, copies rhs_in's bits
-// (g + 0.0 would turn a -0.0 into +0.0).
+// rhs_out = rhs_in + the field term: pn_kernel_accel_term (pn_sim_rhs.h), one workgroup of four waves per GMLS kernel, a read from `accel` (written
+// by k_field_points in the launch before this one).  Every kernel of a state that is inactive, empty or outside all its windows copies rhs_in's bits.
 __global__ void __launch_bounds__(PN_FIELD_THREADS) k_field_rhs(int n_IP, const pn_field_state* __restrict__ st, double dx3, const double* __restrict__ rho,
                                                                 const int* __restrict__ kernel_bg, const int* __restrict__ kernel_cnt,
                                                                 const int* __restrict__ buffer, const double* __restrict__ Nx_csr,
                                                                 const double* __restrict__ rhs_in, double* __restrict__ rhs_out,
                                                                 const double* __restrict__ accel) {
-    __shared__ double s_part[PN_FIELD_WAVES][30];
-    const int kid = blockIdx.x, t = threadIdx.x;
-    const int bg = min(max(kernel_bg[kid], 0), 8 * n_IP), end = min(bg + max(kernel_cnt[kid], 0), 8 * n_IP);
-    const double* g = rhs_in + (size_t)kid * 30;
-    double* o = rhs_out + (size_t)kid * 30;
     const bool on = st->active != 0 && st->n > 0;  // uniform over the launch
-    double acc[30];
-#pragma unroll
-    for (int i = 0; i < 30; i++) acc[i] = 0.0;
-    int hit = 0;
-    if (on) {
-        for (int e = bg + t; e < end; e += PN_FIELD_THREADS) {
-            const int p = buffer[e] >> 3;
-            if ((unsigned)p >= (unsigned)n_IP) continue;  // never with the tables solver.py builds; keeps every read inside its buffer
-            const double a[3] = {accel[(size_t)p * 3], accel[(size_t)p * 3 + 1], accel[(size_t)p * 3 + 2]};
-            if (a[0] == 0.0 && a[1] == 0.0 && a[2] == 0.0) continue;
-            hit = 1;
-            const double m = rho[p] * dx3;
-            const double* N = Nx_csr + (size_t)e * 10;
-#pragma unroll
-            for (int b = 0; b < 10; b++) {
-                const double w = m * N[b];
-#pragma unroll
-                for (int c = 0; c < 3; c++) acc[b * 3 + c] += w * a[c];
-            }
-        }
-    }
-    if (!__syncthreads_or(hit)) {  // uniform over the workgroup
-        if (t < 30) o[t] = g[t];
-        return;
-    }
-#pragma unroll
-    for (int i = 0; i < 30; i++) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) acc[i] += __shfl_down(acc[i], off);
-    }
-    if ((t & 63) == 0) {
-#pragma unroll
-        for (int i = 0; i < 30; i++) s_part[t >> 6][i] = acc[i];
-    }
-    __syncthreads();
-    if (t < 30) {
-        double s = s_part[0][t];
-#pragma unroll
-        for (int w = 1; w < PN_FIELD_WAVES; w++) s += s_part[w][t];
-        o[t] = g[t] + s;
-    }
+    pn_kernel_accel_term<PN_FIELD_THREADS>(blockIdx.x, threadIdx.x, on, n_IP, dx3, rho, kernel_bg, kernel_cnt, buffer, Nx_csr, rhs_in, rhs_out,
+                                           PnAccelRead{accel});
 }
 
 // behind k_field_points and k_field_rhs on the same stream: every thread that reads the clock has read it before it moves

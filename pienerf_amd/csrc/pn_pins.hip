@@ -8,15 +8,16 @@
 #include <math.h>
 
 #include "pn_common.h"
+#include "pn_sim_rhs.h"
 
-static_assert(sizeof(pn_pin_motion) == 128, "pn_pin_motion: 128 bytes (pienerf_amd/simulator/solver.py allocates it as 16 doubles)");
+static_assert(sizeof(pn_pin_motion) == 128, "pn_pin_motion: 128 bytes (pienerf_amd/simulator/pins.py allocates it as 16 doubles)");
 
 #define PN_PIN_THREADS 64   // one wave per GMLS kernel: the sum's tree is the wave's shuffle tree, fixed on every device
 #define PN_2PI 6.283185307179586476925286766559
 
 // ------------------------------------------------------------------------------------------------ the right-hand side, every substep
 // One workgroup per GMLS kernel.  Lane l adds the run's entries l, l + 64, l + 128, ... in ascending order into 30 sums (basis x component), the
-// lanes are added by a shuffle tree (32, 16, ... 1), lane 0's total goes through LDS to the 30 lanes that write.  No atomics: the same bits on
+// lanes are added by pn_wave_sum30 (pn_sim_rhs.h: the shuffle tree 32, 16, ... 1), lane 0's total goes through LDS to the 30 lanes that write.  No atomics: the same bits on
 // every run.  A kernel without an entry, or an inactive state, copies rhs_gravity (g + stiff 0 would turn a -0.0 into +0.0).
 __global__ void __launch_bounds__(PN_PIN_THREADS) k_pin_rhs(int n_pin, const pn_pin_motion* __restrict__ st, double dt, double stiff,
                                                             const double* __restrict__ rhs_gravity, const int* __restrict__ pin_bg,
@@ -63,11 +64,7 @@ __global__ void __launch_bounds__(PN_PIN_THREADS) k_pin_rhs(int n_pin, const pn_
             for (int c = 0; c < 3; c++) acc[b * 3 + c] += w * u[c];
         }
     }
-#pragma unroll
-    for (int i = 0; i < 30; i++) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) acc[i] += __shfl_down(acc[i], off);
-    }
+    pn_wave_sum30(acc);
     if (lane == 0) {
 #pragma unroll
         for (int i = 0; i < 30; i++) s_sum[i] = acc[i];

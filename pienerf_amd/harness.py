@@ -177,7 +177,7 @@ class SimRenderHarness:
             self._sim_stream = torch.cuda.Stream(self.device)
         self._graph_pose = torch.from_numpy(np.asarray(self.pose, np.float32)).unsqueeze(0).to(self.device)
         self._graph_pose_host = self.pose
-        keep = (self.sim.dof.clone(), self.sim.dof_vel.clone(), self.sim._pin_clock_keep(), self.sim._field_clock_keep())
+        keep = self.sim.keep_state()
         warm = torch.cuda.Stream(self.device)
         warm.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(warm):
@@ -188,18 +188,11 @@ class SimRenderHarness:
         self._graph = torch.cuda.CUDAGraph()
         with _capture(self._graph):
             self._graph_out = self._step_body(n_trips, W, H)
-        self.sim.dof.copy_(keep[0])       # warm-up advanced the simulator; capture itself executes nothing
-        self.sim.dof_vel.copy_(keep[1])
-        self.sim._pin_clock_restore(keep[2])   # ... the pin motion's substep clock: the k-th replayed frame sees the clock of the k-th eager step
-        self.sim._field_clock_restore(keep[3])   # ... and the force fields' clock
+        self.sim.restore_state(keep)      # warm-up advanced the simulator and its stages' clocks (the k-th replayed frame sees the clock of the k-th eager step); capture itself executes nothing
         self.sim.reset_warm_start()       # ... and its SVD warm start: a replay from here has the bits of a simulator that never warmed up
         self._graph_trips = n_trips
         self._graph_done = None
-        self._graph_drag = self.sim.drag_enabled   # the substep's k_drag_force launch is in the graph or it is not
-        self._graph_pins = self.sim.pin_enabled    # ... and so is its k_pin_rhs launch (Simulator.enable_pin_motion)
-        self._graph_contact = self.sim.contact_enabled   # ... and its contact launches (Simulator.enable_contact)
-        self._graph_fields = self.sim.fields_enabled     # ... and its force-field launches (Simulator.enable_fields)
-        self._graph_self = self.sim.self_contact_enabled   # ... and its self-contact launches (Simulator.enable_self_contact)
+        self._graph_stages = self.sim.enabled_stage_names()   # a stage's launches (Simulator.STAGES) are in the graph or they are not
         self._graph_overlay = self.model.collider_overlay_key()   # ... and the render's collider overlay, with its style (draw_colliders)
         self._graph_points = self.model.point_overlay_key()   # ... and the point overlay's launch pair (draw_points)
         self._graph_form_epoch = self._net_form_epoch()
@@ -217,24 +210,19 @@ class SimRenderHarness:
             raise RuntimeError(f"the network's weights were refreshed into another arithmetic form (pn_net_form) since {what} was captured: its graphs "
                                f"hold the old form's kernels — capture again")
 
-    def _check_pins_captured(self, captured, what, again):
-        if self.sim.pin_enabled and not captured:
-            raise RuntimeError(f"pin motion: {what} was captured before enable_pin_motion(), its substep ignores the pin motion: {again} again")
+    # a stage enabled after the capture: its state is device memory and is followed without a recapture, its launches must be in the graph
+    _STAGE_NOT_CAPTURED = {
+        "pins": "pin motion: {what} was captured before enable_pin_motion(), its substep ignores the pin motion: {again} again",
+        "contact": "contact: {what} was captured before enable_contact(), its substep ignores the colliders: {again} again",
+        "fields": "fields: {what} was captured before enable_fields(), its substep ignores the force fields: {again} again",
+        "self": "self-contact: {what} was captured before enable_self_contact(), its substep ignores self-contact: {again} again",
+    }
 
-    def _check_contact_captured(self, captured, what, again):
-        """Colliders and parameters changed after a capture need no recapture (the state is device memory); the launch itself must be in the graph."""
-        if self.sim.contact_enabled and not captured:
-            raise RuntimeError(f"contact: {what} was captured before enable_contact(), its substep ignores the colliders: {again} again")
-
-    def _check_fields_captured(self, captured, what, again):
-        """Fields and the clock changed after a capture need no recapture (the state is device memory); the launches themselves must be in the graph."""
-        if self.sim.fields_enabled and not captured:
-            raise RuntimeError(f"fields: {what} was captured before enable_fields(), its substep ignores the force fields: {again} again")
-
-    def _check_self_captured(self, captured, what, again):
-        """Parameters changed after a capture need no recapture (the state is device memory); the launches themselves must be in the graph."""
-        if self.sim.self_contact_enabled and not captured:
-            raise RuntimeError(f"self-contact: {what} was captured before enable_self_contact(), its substep ignores self-contact: {again} again")
+    def _check_stages_captured(self, captured, what, again):
+        now = self.sim.enabled_stage_names()
+        for name, msg in self._STAGE_NOT_CAPTURED.items():
+            if name in now and name not in captured:
+                raise RuntimeError(msg.format(what=what, again=again))
 
     def _check_overlay_captured(self, captured, what, again):
         """The colliders' state is device memory and is followed without a recapture; the overlay's launch, its style and t_max are in the graph."""
@@ -364,10 +352,7 @@ class SimRenderHarness:
         if getattr(self, "_graph", None) is None:
             self.capture()
         self._check_net_form(self._graph_form_epoch, "the step")
-        self._check_pins_captured(self._graph_pins, "the step graph", "capture()")
-        self._check_contact_captured(self._graph_contact, "the step graph", "capture()")
-        self._check_fields_captured(getattr(self, "_graph_fields", False), "the step graph", "capture()")
-        self._check_self_captured(getattr(self, "_graph_self", False), "the step graph", "capture()")
+        self._check_stages_captured(self._graph_stages, "the step graph", "capture()")
         self._check_overlay_captured(self._graph_overlay, "the step graph", "capture()")
         self._check_points_captured(getattr(self, "_graph_points", None), "the step graph", "capture()")
         self._check_previous_graph_frame()
@@ -380,7 +365,7 @@ class SimRenderHarness:
         self.frame += 1
         if pose is not None:
             self._graph_pose_host = pose
-        if self._graph_drag:
+        if "drag" in self._graph_stages:
             g = self._graph_out
             self._drag_frame = ("graph", g["depth_0"][0], g["_ip"][0], self._graph_pose_host, self.intrinsics)
         else:
@@ -480,11 +465,7 @@ class SimRenderHarness:
                                    sim_owner=sim_owner, dedicated_sim=dedicated_sim, copy_out=copy_out, on_retire=on_retire,
                                    force_collectives=bool(_force_collectives) and on, sim_on_lanes=sim_on_lanes)
         self.sim.force_hooks = (self._pipe.before_force, self._pipe.after_force) if self._pipe.sim_on_lanes else None
-        self._pipe_drag = self.sim.drag_enabled
-        self._pipe_pins = self.sim.pin_enabled
-        self._pipe_contact = self.sim.contact_enabled
-        self._pipe_fields = self.sim.fields_enabled
-        self._pipe_self = self.sim.self_contact_enabled
+        self._pipe_stages = self.sim.enabled_stage_names()
         self._pipe_overlay = self.model.collider_overlay_key()
         self._pipe_points = self.model.point_overlay_key()
         self._pipe_single = not frame_parallel and not (render_kw or {}).get("ray_batch")
@@ -501,10 +482,7 @@ class SimRenderHarness:
     @torch.no_grad()
     def step_pipelined(self, pose=None):
         self._check_net_form(self._pipe_form_epoch, "the pipeline")
-        self._check_pins_captured(self._pipe_pins, "the pipeline", "capture_pipelined()")
-        self._check_contact_captured(self._pipe_contact, "the pipeline", "capture_pipelined()")
-        self._check_fields_captured(getattr(self, "_pipe_fields", False), "the pipeline", "capture_pipelined()")
-        self._check_self_captured(getattr(self, "_pipe_self", False), "the pipeline", "capture_pipelined()")
+        self._check_stages_captured(self._pipe_stages, "the pipeline", "capture_pipelined()")
         if not getattr(self, "_pipe_single", True):
             self._refuse_overlay_form("the frame-parallel / staged pipeline")
             self._refuse_points_form("the frame-parallel / staged pipeline")
@@ -655,9 +633,9 @@ class SimRenderHarness:
         mode = getattr(self, "_drag_frame", None)
         if mode is None:
             raise RuntimeError("drag: no frame has been rendered yet (the cursor is unprojected against the last frame's depth_0)")
-        if mode[0] == "graph" and not getattr(self, "_graph_drag", False):
+        if mode[0] == "graph" and not self._graph_drag:
             raise RuntimeError("drag: the step graph was captured before enable_drag(), its substep ignores the drag state: capture() again")
-        if mode[0] == "pipelined" and not getattr(self, "_pipe_drag", False):
+        if mode[0] == "pipelined" and not self._pipe_drag:
             raise RuntimeError("drag: the pipeline was captured before enable_drag(), its substep ignores the drag state: capture_pipelined() again")
         return mode
 
@@ -697,6 +675,12 @@ class SimRenderHarness:
     def to_host(self, out):
         """The reference's device->host boundary (trainer.py:589-592)."""
         return {k: out[k][0].detach().cpu().numpy() for k in ("image", "depth", "depth_0")}
+
+
+# h._graph_fields, h._pipe_drag, ...: whether the stage's launches are in the step graph / the pipeline's substep graph (False before a capture)
+for _form in ("_graph", "_pipe"):
+    for _st in Simulator.STAGES:
+        setattr(SimRenderHarness, f"{_form}_{_st.name}", property(lambda self, _f=_form + "_stages", _n=_st.name: _n in getattr(self, _f, ())))
 
 
 class _HipStream:
@@ -834,7 +818,7 @@ class _HipBackend:
         self.pose_pin = [pose0.clone().pin_memory() for _ in range(n_ws)]
         self.pose_key = [pose0.numpy().tobytes()] * n_ws
         self.ip = [tuple(torch.empty((n_IP, c), dtype=torch.float32, device=dev) for c in (3, 9, 27)) for _ in range(n_ws)]
-        keep = (sim.dof.clone(), sim.dof_vel.clone(), sim._pin_clock_keep(), sim._field_clock_keep())
+        keep = sim.keep_state()
         main = torch.cuda.current_stream(dev)
         for ws in range(n_ws):  # warm-up of every workspace outside capture (creates the pn_frame workspaces, the fp16 tables, ...)
             s = self._streams[f"lane{ws // depth}"]
@@ -902,10 +886,7 @@ class _HipBackend:
                     check(lib().pn_copier_submit(self.copier, ctypes.c_void_p(hb.data_ptr()), ctypes.c_void_p(self.packed[ws].data_ptr()),
                                                  hb.numel() * hb.element_size(), None, ctypes.byref(t)), "copier_submit")
                     check(lib().pn_copier_wait(self.copier, t.value), "copier_wait")
-        sim.dof.copy_(keep[0])      # warm-up advanced the simulator; capture itself executes nothing
-        sim.dof_vel.copy_(keep[1])
-        sim._pin_clock_restore(keep[2])   # ... the pin motion's substep clock
-        sim._field_clock_restore(keep[3])   # ... and the force fields'
+        sim.restore_state(keep)    # warm-up advanced the simulator and its stages' clocks; capture itself executes nothing
         sim.reset_warm_start()     # ... and its SVD warm start: a replay from here has the bits of a simulator that never warmed up
         torch.cuda.synchronize(dev)
 

@@ -253,6 +253,28 @@ def test_setters_refuse_bad_arguments():
     assert rhs(out=d) == PN_ERR_ARG                                                             # rhs_out is another buffer than rhs_in
 
 
+def test_the_shared_sum_is_in_library_header_and_signatures_and_refuses_bad_arguments():
+    """pn_sim_accel_rhs: the per-kernel sum of contact, fields and self-contact on its own (csrc/pn_sim_rhs.h; tests/test_gpu_rhs_term.py runs it)."""
+    from pienerf_amd import _lib
+    n = "pn_sim_accel_rhs"
+    assert re.search(r"\b" + n + r"\s*\(", _header()) and hasattr(ctypes.CDLL(_lib.LIB_PATH), n)
+    i32, f64, P = _lib.SIGNATURES["pn_sim_contact_rhs"][1][0], _lib.SIGNATURES["pn_sim_contact_rhs"][1][3], _lib.SIGNATURES["pn_sim_contact_rhs"][1][2]
+    assert _lib.SIGNATURES[n] == (i32, [i32, i32, f64] + [P] * 9)
+    h, d, out = _lib.lib(), ctypes.c_void_p(16), ctypes.c_void_p(32)
+
+    def rhs(n_k=4, n_IP=3, dx=0.1, null=None, rin=d, rout=out):
+        p = [d] * 6 + [rin, rout]          # rho, kernel_bg, kernel_cnt, buffer, Nx_csr, accel | rhs_in, rhs_out
+        if null is not None:
+            p[null] = None
+        return h.pn_sim_accel_rhs(n_k, n_IP, dx, *p, None)
+    for i in range(8):
+        assert rhs(null=i) == PN_ERR_ARG, i                                                      # a NULL pointer, whichever
+    assert rhs(rout=d) == PN_ERR_ARG                                                             # rhs_out is another buffer than rhs_in
+    assert rhs(dx=0.0) == PN_ERR_ARG and rhs(dx=-1.0) == PN_ERR_ARG and rhs(dx=float("nan")) == PN_ERR_ARG and rhs(dx=float("inf")) == PN_ERR_ARG
+    assert rhs(n_k=0) == PN_ERR_ARG and rhs(n_IP=0) == PN_ERR_ARG and rhs(n_IP=(1 << 27) + 1) == PN_ERR_ARG
+    assert b"argument check failed" in h.pn_last_error()
+
+
 # ---------------------------------------------------------------- the Simulator's side
 def _cpu_sim(dx=0.1):
     from pienerf_amd.simulator.solver import Simulator
