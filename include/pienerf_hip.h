@@ -665,6 +665,71 @@ int pn_sim_contact_rhs(int n_k, int n_IP, const void* state, double dt, double d
 int pn_sim_accel_rhs(int n_k, int n_IP, double dx, const double* rho, const int* kernel_bg, const int* kernel_cnt, const int* buffer,
                      const double* Nx_csr, const double* accel, const double* rhs_in, double* rhs_out, void* stream);
 
+/* Rigid balls (csrc/pn_bodies.hip; Simulator.enable_bodies / add_body): up to 8 dynamic spheres the object pushes back.  A dynamic
+ * body b is bound to slot b of a pn_contact_state that holds a solid sphere (PN_CONTACT_SPHERE, radius R); it has a mass M > 0 and a linear damping
+ * c >= 0 (1/s).  Its centre p and velocity u ARE the slot's p and v: there is no second copy, so contact, the drawn frame and the shadows follow a
+ * moving ball without a change.  Two launches in front of every substep, behind contact's, evaluate everything from the state the substep starts from:
+ *   1. object side: unchanged.  pn_sim_contact_rhs has evaluated its law against slot b with col->v = u.
+ *   2. reaction: F_b = - sum_i m_i a_{i,b} over the integration points, m_i = rho[i] dx^3, a_{i,b} = a_n nh - a_t w_t / |w_t| slot b's own part of
+ *      the contact law at point i (x_i, v_i as above; the contact state's kappa, beta, mu, h), and delta_max,b = the largest delta among the points
+ *      slot b penetrates (0: none).  The sum's order is fixed: workgroups of 256 points in point order, in each a wave's shuffle tree 32, 16 ... 1 and
+ *      then the waves as ((w0 + w1) + w2) + w3, the workgroups' partials added in ascending workgroup order.  No atomics; the bits do not depend on
+ *      the device.
+ *   3. clamp: s = min(1, M delta_max / (dt^2 |F_b|)) (s = 1 when F_b = 0), so the body's own response dt^2 s |F_b| / M to its reaction is at most
+ *      its deepest penetration: the counterpart of dt^2 a_n <= (kappa + beta) delta for a point.  A (substep, body) pair with s < 1 is counted.
+ *   4. static colliders: every other slot that is not a dynamic body (planes, solid spheres, the container) acts on the ball through the same law,
+ *      applied at the point p with velocity u and the ball's radius in the thickness's place (kappa, beta, mu of the contact state; velocity relative
+ *      to that collider's v): plane d = n.(p - p_c) - R, solid sphere d = |p - p_c| - R_c - R, container d = R_c - |p - p_c| - R, delta = max(-d, 0),
+ *      slots in index order, giving a_static.  Static colliders get no reaction; two dynamic balls pass through each other.
+ *   5. integration, semi-implicit like the object's: u+ = (u + dt (g + s F_b / M + a_static)) / (1 + dt c), p+ = p + dt u+, both written into the
+ *      slot; the substep clock k advances.
+ * No rotation: the spheres have no spin and friction gives no torque.  With active = 0, or with the contact state inactive, no body moves (the clock
+ * still counts).  Layout of the state: */
+#define PN_BODIES_SLOTS 8          /* = PN_CONTACT_SLOTS: body b lives in collider slot b */
+typedef struct pn_body {
+    int dynamic;       /* 1: slot b of the contact state is a dynamic body (it acts only while that slot holds a PN_CONTACT_SPHERE) */
+    int reserved;
+    double M;          /* mass, > 0 */
+    double c;          /* linear damping, 1/s, >= 0 */
+    double F[3];       /* the last substep's raw reaction F_b */
+    double s;          /* ... its clamp scale, in (0, 1] */
+    double delta_max;  /* ... its deepest penetration */
+    int64_t clamped;   /* substeps with s < 1 since the body was made dynamic */
+} pn_body;
+typedef struct pn_bodies_state {
+    int64_t k;         /* substeps the stage has run */
+    int active;        /* 0: no body moves */
+    int reserved;
+    double g[3];       /* gravity on the bodies */
+    pn_body b[PN_BODIES_SLOTS];
+} pn_bodies_state;
+uint64_t pn_sim_bodies_bytes(void);      /* sizeof(pn_bodies_state) = 616 */
+/* Bytes of pn_sim_bodies_step's `work` for n_IP points: 32 doubles (F[3], delta_max for 8 slots) per workgroup of 256 points, and 8 bytes behind
+ * them for the one-launch form's arrival counter; 0 for n_IP outside 1 .. 2^27. */
+uint64_t pn_sim_bodies_work_bytes(int n_IP);
+/* Writes `active` (>= 0; -1 keeps it) and, with gravity3_host != NULL, g (finite, else PN_ERR_ARG).  A one-thread launch on `stream`. */
+int pn_sim_bodies_set_params(void* state, int active, const double* gravity3_host, void* stream);
+/* Slot `slot` (0 .. 7): dynamic 1 makes it a body of `mass` (finite, > 0) and `damping` (finite, >= 0), else PN_ERR_ARG; a slot that was not
+ * dynamic before starts with F = 0, s = 1, delta_max = 0, clamped = 0, one that was keeps them.  dynamic 0 clears the record (mass and damping are
+ * ignored).  A one-thread launch on `stream`. */
+int pn_sim_bodies_set_body(void* state, int slot, int dynamic, double mass, double damping, void* stream);
+/* Overwrites the centre (mask & 1) and / or the velocity (mask & 2) of slot `slot` in `contact_state` (a pn_contact_state) with pv6_host = (p[3],
+ * v[3]), finite; mask in 1 .. 3, else PN_ERR_ARG.  What is not in the mask keeps the device's value.  A one-thread launch on `stream`. */
+int pn_sim_bodies_set_motion(void* contact_state, int slot, int mask, const double* pv6_host, void* stream);
+/* The next substep is substep k >= 0 of the stage's clock.  A one-thread launch on `stream`. */
+int pn_sim_bodies_clock(void* state, int64_t k, void* stream);
+/* One substep of every dynamic body.  one_launch 0, TWO launches, the measured faster form: k_body_reaction, a thread per
+ * integration point in workgroups of 256, writes each workgroup's (F[3], delta_max) per slot into `work` (every word the second launch reads is
+ * written by the first, zeros for a workgroup none of whose points touches a body); k_body_step, one workgroup, adds the partials in ascending order
+ * and does steps 3 - 5 for the slots 0 .. 7.  one_launch 1: ONE launch, in which the workgroup that arrives last at a counter does k_body_step's work
+ * behind an agent-scope release / acquire pair — the same sums in the same order, the same bits.  `work`: pn_sim_bodies_work_bytes(n_IP) bytes,
+ * 8-byte aligned; the partials may hold anything on entry, the counter in its last 8 bytes is zero before the first call and left zero by every call.
+ * `state` a pn_bodies_state and `contact_state` the pn_contact_state, both device memory; dof, dof_vel, topo, rho, Nx as pn_sim_contact_rhs's.
+ * PN_ERR_ARG, before anything is enqueued, for a NULL pointer, dt or dx not finite and > 0, n_IP outside 1 .. 2^27, one_launch not 0 or 1.  No
+ * allocation, no host synchronisation, capturable. */
+int pn_sim_bodies_step(int n_k, int n_IP, void* state, void* contact_state, void* work, double dt, double dx, const double* dof, const double* dof_vel,
+                       const int* topo, const double* rho, const double* Nx, int one_launch, void* stream);
+
 /* Force fields (csrc/pn_fields.hip; Simulator.enable_fields): wind, vortex and blast on the whole body, with air drag.  A fourth
  * right-hand-side stage beside drag, pins and contact: launches in front of every substep write rhs_out = rhs_in + the field term of the state and the
  * time that substep starts from, and the substep takes rhs_out in its rhs_gravity slot; the matrix, Ainv and the substep's kernels stay as they are.

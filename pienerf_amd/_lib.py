@@ -145,6 +145,13 @@ SIGNATURES = {
     "pn_sim_contact_set_collider": (i32, [P, i32, i32, P, P]),
     "pn_sim_contact_rhs": (i32, [i32, i32, P, f64, f64, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "pn_sim_accel_rhs": (i32, [i32, i32, f64, P, P, P, P, P, P, P, P, P]),
+    "pn_sim_bodies_bytes": (u64, []),
+    "pn_sim_bodies_work_bytes": (u64, [i32]),
+    "pn_sim_bodies_set_params": (i32, [P, i32, P, P]),
+    "pn_sim_bodies_set_body": (i32, [P, i32, i32, f64, f64, P]),
+    "pn_sim_bodies_set_motion": (i32, [P, i32, i32, P, P]),
+    "pn_sim_bodies_clock": (i32, [P, C.c_int64, P]),
+    "pn_sim_bodies_step": (i32, [i32, i32, P, P, P, f64, f64, P, P, P, P, P, i32, P]),
     "pn_sim_fields_bytes": (u64, []),
     "pn_sim_fields_set_active": (i32, [P, i32, P]),
     "pn_sim_fields_set_field": (i32, [P, i32, i32, P, P]),

@@ -51,6 +51,9 @@ UNITS = {
     # pn_sim.hip shares: a point's position as update_F sums it), so the three contract alike and the bits agree; fp64 sums in a fixed order
     "pn_contact.hip": ["-ffp-contract=fast"],
     "pn_fields.hip": ["-ffp-contract=fast"],
+    # the rigid balls: the per-collider law (pn_contact_law.h) and a point's state (pn_sim_rhs.h) are contact's own lines, contracted alike, so slot
+    # b's term at a point is the same bits on the object's side and in the ball's reaction
+    "pn_bodies.hip": ["-ffp-contract=fast"],
     # the one decision self-contact takes in floating point (a pair's eligibility at rest) switches contraction off for itself
     "pn_selfcontact.hip": ["-ffp-contract=fast"],
     # the colliders drawn into a frame: per-ray fp32 with decisions in it (hit / miss, checker parity, in front of / behind the object), one rounding per

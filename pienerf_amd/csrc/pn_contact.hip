@@ -9,6 +9,7 @@
 #include <math.h>
 
 #include "pn_common.h"
+#include "pn_contact_law.h"
 #include "pn_sim_rhs.h"
 
 static_assert(sizeof(pn_contact_collider) == 88, "pn_contact_collider: 88 bytes (pienerf_amd/simulator/contact.py: CONTACT_COLLIDER_DTYPE)");
@@ -24,41 +25,9 @@ __device__ __forceinline__ bool pn_contact_law(const pn_contact_state* __restric
     const double kappa = st->kappa, beta = st->beta, mu = st->mu, h = st->h, dt2 = dt * dt;
     bool hit = false;
     a[0] = a[1] = a[2] = 0.0;
-    for (int c = 0; c < n; c++) {
-        const pn_contact_collider* col = st->c + c;
-        const int type = col->type;
-        if (type < PN_CONTACT_PLANE || type > PN_CONTACT_CONTAINER) continue;
-        double nh[3], d;
-        const double r0 = x[0] - col->p[0], r1 = x[1] - col->p[1], r2 = x[2] - col->p[2];
-        if (type == PN_CONTACT_PLANE) {
-            nh[0] = col->n[0]; nh[1] = col->n[1]; nh[2] = col->n[2];
-            d = nh[0] * r0 + nh[1] * r1 + nh[2] * r2;
-        } else {
-            const double L = sqrt(r0 * r0 + r1 * r1 + r2 * r2);
-            if (L > 0.0) {
-                nh[0] = r0 / L; nh[1] = r1 / L; nh[2] = r2 / L;
-            } else {
-                nh[0] = 0.0; nh[1] = 1.0; nh[2] = 0.0;
-            }
-            d = L - col->R;
-            if (type == PN_CONTACT_CONTAINER) {
-                d = -d;
-                nh[0] = -nh[0]; nh[1] = -nh[1]; nh[2] = -nh[2];
-            }
-        }
-        const double delta = h - d;
-        if (!(delta > 0.0)) continue;
-        hit = true;
-        const double w0 = v[0] - col->v[0], w1 = v[1] - col->v[1], w2 = v[2] - col->v[2];
-        const double wn = w0 * nh[0] + w1 * nh[1] + w2 * nh[2];
-        const double t0 = w0 - wn * nh[0], t1 = w1 - wn * nh[1], t2 = w2 - wn * nh[2];
-        const double an = (kappa * delta + beta * fmin(fmax(-wn, 0.0) * dt, delta)) / dt2;
-        a[0] += an * nh[0]; a[1] += an * nh[1]; a[2] += an * nh[2];
-        const double wt = sqrt(t0 * t0 + t1 * t1 + t2 * t2);
-        if (wt > 0.0) {
-            const double at = fmin(mu * an, wt / dt), s = at / wt;
-            a[0] -= s * t0; a[1] -= s * t1; a[2] -= s * t2;
-        }
+    for (int c = 0; c < n; c++) {   // one collider's part: pn_contact_law.h, shared with the rigid balls (pn_bodies.hip)
+        double delta;
+        if (pn_contact_collider_term(st->c + c, kappa, beta, mu, h, dt, dt2, x, v, a, &delta)) hit = true;
     }
     return hit;
 }

@@ -110,6 +110,7 @@ class SimRenderHarness:
                 main.wait_event(self._sim_done)            # the previous substep must have finished before dof is read
             IP_pos, IP_F, IP_dF = self.sim.get_IP_info()
             m.p_def, m.IP_F, m.IP_dF = IP_pos, IP_F, IP_dF
+            self._snapshot_colliders()   # enable_bodies(): the balls this frame draws, as the substep below finds them
             if self.overlap_sim:
                 # the substep only feeds the NEXT frame (render lags sim by one frame, trainer.py:300-318), so it runs on a
                 # side stream concurrently with this frame's render
@@ -149,6 +150,7 @@ class SimRenderHarness:
         rays = get_rays(self._graph_pose, self.intrinsics, H, W, -1)
         IP_pos, IP_F, IP_dF = self.sim.get_IP_info()
         m.p_def, m.IP_F, m.IP_dF = IP_pos, IP_F, IP_dF
+        self._snapshot_colliders()   # enable_bodies(): the balls this frame draws, as the substep below finds them
         self._sim_stream.wait_stream(main)
         with torch.cuda.stream(self._sim_stream):
             self.sim.stepforward()
@@ -214,6 +216,7 @@ class SimRenderHarness:
     _STAGE_NOT_CAPTURED = {
         "pins": "pin motion: {what} was captured before enable_pin_motion(), its substep ignores the pin motion: {again} again",
         "contact": "contact: {what} was captured before enable_contact(), its substep ignores the colliders: {again} again",
+        "bodies": "bodies: {what} was captured before enable_bodies(), its substep does not move the balls: {again} again",
         "fields": "fields: {what} was captured before enable_fields(), its substep ignores the force fields: {again} again",
         "self": "self-contact: {what} was captured before enable_self_contact(), its substep ignores self-contact: {again} again",
     }
@@ -297,11 +300,33 @@ class SimRenderHarness:
         4.11).  `style`: a ColliderStyle (None: pienerf_amd.colliders.collider_style for the colliders present now, no checker).  Call it BEFORE
         capture() / capture_pipelined(): a graph captured without the launch is refused.  step, capture / step_graph and the single-process
         capture_pipelined draw them (the pipeline draws the LIVE state: a collider moved by the host can appear up to sim_ahead frames early); the
-        frame-parallel, tile-parallel and staged forms raise while an overlay is set.  ValueError before Simulator.enable_contact()."""
+        frame-parallel, tile-parallel and staged forms raise while an overlay is set.  ValueError before Simulator.enable_contact().  With the rigid
+        balls enabled (Simulator.enable_bodies) the substep itself moves collider slots while the frame renders beside it, so the overlay then reads a
+        copy of the state taken with the frame's DOF snapshot (_snapshot_colliders): frame f shows ball and object at the same substep."""
         from .colliders import collider_style
         state = self.sim.collider_state()
-        self.model.set_collider_overlay(state, collider_style(types=self.sim.collider_types()) if style is None else style, t_max)
+        self._collider_snapshot = state.clone() if self.sim.bodies_enabled else None
+        self.model.set_collider_overlay(state if self._collider_snapshot is None else self._collider_snapshot,
+                                        collider_style(types=self.sim.collider_types()) if style is None else style, t_max)
         return self
+
+    def _snapshot_colliders(self):
+        """With balls and an overlay: the collider state this frame draws, copied on the current stream behind the previous substep and in front of
+        this frame's (one 744-byte device copy, captured with the step).  An overlay set before enable_bodies() reads the live state: it is moved
+        onto a copy here, which a graph captured with the live buffer refuses as a changed overlay.  Nothing is enqueued otherwise."""
+        ov = getattr(self.model, "_overlay", None)
+        if ov is None or not self.sim.bodies_enabled:
+            return
+        live = self.sim.collider_state()
+        if getattr(self, "_collider_snapshot", None) is None or ov[0] is not self._collider_snapshot:
+            self._collider_snapshot = live.clone()
+            self.model.set_collider_overlay(self._collider_snapshot, ov[1], ov[2])
+        self._collider_snapshot.copy_(live)
+
+    def _refuse_bodies_overlay_pipelined(self):
+        if self.sim.bodies_enabled and self.model.collider_overlay_key() is not None:
+            raise RuntimeError("bodies: the pipelined form draws the live collider state, which would show a ball sim_ahead frames in front of the object "
+                               "it touches; step() and capture() / step_graph() draw the balls; hide_colliders() first")
 
     def _order_overlay_behind_setters(self):
         """set_collider's one-thread launch runs on the simulator's force stream; a frame that draws the colliders reads the state on the render's
@@ -442,6 +467,7 @@ class SimRenderHarness:
             self._refuse_overlay_form("the staged form")
             self._refuse_points_form("the staged form")
         self._refuse_shadows_pipelined()
+        self._refuse_bodies_overlay_pipelined()
         o = self.opt
         W, H = W or o["W"], H or o["H"]
         on = bool(frame_parallel) and dist.is_available() and dist.is_initialized()
@@ -487,6 +513,7 @@ class SimRenderHarness:
             self._refuse_overlay_form("the frame-parallel / staged pipeline")
             self._refuse_points_form("the frame-parallel / staged pipeline")
         self._refuse_shadows_pipelined()
+        self._refuse_bodies_overlay_pipelined()
         self._check_overlay_captured(getattr(self, "_pipe_overlay", None), "the pipeline", "capture_pipelined()")
         self._check_points_captured(getattr(self, "_pipe_points", None), "the pipeline", "capture_pipelined()")
         out = self._pipe.step(pose)

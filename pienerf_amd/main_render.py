@@ -5,7 +5,7 @@ deformed point cloud and the per-frame IP state the reference's ``main_render.py
     python -m pienerf_amd.main_render --frames 30 --out output_img/chair [--ply model/chair_0.ply] [--ckpt ws/checkpoints/ngp_ep0300.pth]
            [--W 800 --H 800] [--radius 5 --azimuth 0 --elevation 0 --fovy 50] [--force fx fy fz | --drag X0 Y0 X1 Y1] [--pin_shake AX AY AZ HZ] [--pin_twist NX NY NZ DEG HZ [--pin_centre X Y Z]] [--save_ply] [--save_ip_state]
            [--floor Y] [--collide_sphere CX CY CZ R]... [--collide_inside CX CY CZ R] [--contact_stiffness 0.5 --contact_damping 0.5 --friction 0.5
-           --contact_thickness DX/2] [--unpin]
+           --contact_thickness DX/2] [--unpin] [--ball CX CY CZ R MASS [VX VY VZ]]... [--ball_damping C]
            [--wind WX WY WZ [--wind_drag 2] [--gust G HZ] [--gust_wave KX KY KZ]] [--air_drag C] [--vortex PX PY PZ NX NY NZ OMEGA RADIUS]...
            [--blast CX CY CZ STRENGTH RADIUS T0 T1]...
            [--self_contact [--self_thickness H] [--self_exclusion R] [--self_stiffness 0.5] [--self_damping 0.5] [--self_friction 0]]
@@ -25,6 +25,9 @@ with --force / --drag, and images, --save_ply and --save_mesh follow the moving 
 --floor / --collide_sphere / --collide_inside give the object something to meet (Simulator.enable_contact): a floor at height Y, solid
 spheres (repeatable), a container sphere the object stays inside; --unpin clears every pin of the cloud, so the object can be dropped.  They compose with
 --force, --drag, --pin_*, --save_ply and --save_mesh.
+--ball adds a dynamic ball the object pushes back (Simulator.enable_bodies / add_body; repeatable): a solid sphere of radius R and mass
+MASS at (CX, CY, CZ), thrown with (VX, VY, VZ) when given, slowed by --ball_damping per second; it falls under the simulator's gravity, meets the floor
+and the other colliders, and --draw_colliders / --shadows draw it where it is.  It enables contact by itself and composes with every other flag.
 --wind / --air_drag / --vortex / --blast put force fields on the whole body (Simulator.enable_fields): a wind of velocity (WX, WY, WZ)
 that drags the object along at --wind_drag per second, gusting by --gust G HZ (and travelling through space with --gust_wave); still air that damps it
 at --air_drag per second; vortices (repeatable) and blasts with a time window (repeatable).  They compose with everything else.
@@ -97,7 +100,24 @@ def bind_rest_mesh(h, args):
 
 
 def wants_contact(args):
-    return args.floor is not None or bool(args.collide_sphere) or args.collide_inside is not None
+    return args.floor is not None or bool(args.collide_sphere) or args.collide_inside is not None or bool(getattr(args, "ball", None))
+
+
+def ball_specs(args):
+    """--ball / --ball_damping as a list of add_body's arguments; SystemExit for a --ball that has not 5 or 8 numbers or --ball_damping without one."""
+    balls = getattr(args, "ball", None) or []
+    damping = getattr(args, "ball_damping", None)
+    if not balls:
+        if damping is not None:
+            raise SystemExit("--ball_damping needs --ball")
+        return []
+    out = []
+    for b in balls:
+        if len(b) not in (5, 8):
+            raise SystemExit(f"--ball takes CX CY CZ R MASS [VX VY VZ]: 5 or 8 numbers, got {len(b)}")
+        out.append(dict(centre=tuple(b[:3]), radius=b[3], mass=b[4], velocity=tuple(b[5:8]) if len(b) == 8 else None,
+                        damping=0.0 if damping is None else damping))
+    return out
 
 
 def configure_contact(sim, args):
@@ -105,7 +125,8 @@ def configure_contact(sim, args):
     without a collider argument."""
     if not wants_contact(args):
         if any(v is not None for v in (args.contact_stiffness, args.contact_damping, args.friction, args.contact_thickness)):
-            raise SystemExit("--contact_stiffness / --contact_damping / --friction / --contact_thickness need --floor, --collide_sphere or --collide_inside")
+            raise SystemExit("--contact_stiffness / --contact_damping / --friction / --contact_thickness need --floor, --collide_sphere, --collide_inside "
+                             "or --ball")
         return []
     d = lambda v, dflt: dflt if v is None else v
     ids = []
@@ -118,7 +139,11 @@ def configure_contact(sim, args):
             ids.append(sim.add_sphere(c[:3], c[3]))
         if args.collide_inside is not None:
             ids.append(sim.add_sphere(args.collide_inside[:3], args.collide_inside[3], inside=True))
-    except ValueError as e:   # a parameter out of range, a radius <= 0, a ninth collider
+        balls = ball_specs(args)
+        if balls:   # behind the static colliders: --collider_color's slot order stays floor, spheres, container, then the balls
+            sim.enable_bodies()
+            ids.extend(sim.add_body(**b) for b in balls)
+    except ValueError as e:   # a parameter out of range, a radius <= 0, a mass <= 0, a ninth collider
         raise SystemExit(f"contact: {e}")
     return ids
 
@@ -180,7 +205,7 @@ def configure_overlay(h, args):
             raise SystemExit("--collider_color / --checker need --draw_colliders")
         return None
     if not wants_contact(args):
-        raise SystemExit("--draw_colliders needs --floor, --collide_sphere or --collide_inside")
+        raise SystemExit("--draw_colliders needs --floor, --collide_sphere, --collide_inside or --ball")
     from .colliders import collider_style
     try:
         style = collider_style(rgb=args.collider_color, types=h.sim.collider_types(), checker=2.0 * args.sim_dx if args.checker is None else args.checker)
@@ -231,7 +256,7 @@ def configure_points(h, args):
 def check_overlay_args(args):
     """What configure_overlay refuses, before anything is built."""
     if args.draw_colliders and not wants_contact(args):
-        raise SystemExit("--draw_colliders needs --floor, --collide_sphere or --collide_inside")
+        raise SystemExit("--draw_colliders needs --floor, --collide_sphere, --collide_inside or --ball")
     if not args.draw_colliders and (args.collider_color or args.checker is not None):
         raise SystemExit("--collider_color / --checker need --draw_colliders")
     if args.shadows and not args.draw_colliders:
@@ -299,6 +324,7 @@ def run(args):
         raise SystemExit("--pin_centre is the centre of --pin_twist")
     check_overlay_args(args)
     check_self_contact_args(args)
+    ball_specs(args)
     h = build_harness(args)
     pose = scene.orbit_pose(args.radius, args.azimuth, args.elevation)
     os.makedirs(args.out, exist_ok=True)
@@ -368,6 +394,10 @@ def run(args):
             print(f"video: {args.frames} frames, {video.bytes} bytes of JPEG -> {os.path.abspath(video.path)}")
     if h.sim.contact_enabled and not args.quiet:
         print(f"contact: {h.sim.contact_count()} of {h.sim.n_IP} integration points in contact in the last substep")
+    if h.sim.bodies_enabled and not args.quiet:
+        for i, b in h.sim.body_state().items():
+            print(f"ball {i}: centre ({b['centre'][0]:.4f}, {b['centre'][1]:.4f}, {b['centre'][2]:.4f}), speed {float(np.linalg.norm(b['velocity'])):.4f}, "
+                  f"{b['clamped']} substeps clamped")
     if h.sim.self_contact_enabled and not args.quiet:
         print(f"self-contact: {h.sim.self_contact_count()} of {h.sim.n_IP} integration points in contact with the body itself in the last substep, "
               f"{h.sim.self_contact_overflows()} substeps over the bucket cap")
@@ -413,6 +443,9 @@ def parser():
     ap.add_argument("--collide_sphere", type=float, nargs=4, action="append", default=None, metavar=("CX", "CY", "CZ", "R"),
                     help="a solid sphere the object collides with; repeatable")
     ap.add_argument("--collide_inside", type=float, nargs=4, default=None, metavar=("CX", "CY", "CZ", "R"), help="a container sphere the object stays inside")
+    ap.add_argument("--ball", type=float, nargs="+", action="append", default=None, metavar="N",
+                    help="CX CY CZ R MASS [VX VY VZ]: a dynamic ball the object pushes back (DESIGN.md 4.17); repeatable")
+    ap.add_argument("--ball_damping", type=float, default=None, metavar="C", help="linear damping of every --ball, 1/s, >= 0 (default 0)")
     ap.add_argument("--contact_stiffness", type=float, default=None, help="share of a penetration removed per substep, in (0, 1] (default 0.5)")
     ap.add_argument("--contact_damping", type=float, default=None, help="share of the approach velocity removed per substep, in [0, 1] (default 0.5)")
     ap.add_argument("--friction", type=float, default=None, help="Coulomb friction coefficient of the colliders, >= 0 (default 0.5)")

@@ -1,4 +1,4 @@
-"""What the simulator's substep stages (drag.py, pins.py, contact.py, fields.py, selfcontact.py) have in common, written once.
+"""What the simulator's substep stages (drag.py, pins.py, contact.py, bodies.py, fields.py, selfcontact.py) have in common, written once.
 
 A stage is a small state in device memory plus launches that ``Simulator.stepforward`` enqueues in front of the substep.  Each stage's module
 describes it with a ``Stage`` record and holds a mixin with its methods; ``StageHost`` — a base of ``Simulator`` — holds the scaffold those mixins
@@ -118,8 +118,13 @@ class StageHost:
 
     def keep_state(self):
         """dof, dof_vel and the substep clock of every stage that has one, as device copies: for whoever warms the substep up (a capture) or replays
-        a trajectory, and then calls restore_state()."""
-        return dict(dof=self.dof.clone(), dof_vel=self.dof_vel.clone(), clocks=[(st, self._clock_keep(st)) for st in self.STAGES if st.clock])
+        a trajectory, and then calls restore_state().  With the rigid balls enabled (bodies.py) their state and the contact state are kept too: a
+        ball's position and velocity are part of the trajectory."""
+        keep = dict(dof=self.dof.clone(), dof_vel=self.dof_vel.clone(), clocks=[(st, self._clock_keep(st)) for st in self.STAGES if st.clock])
+        moved = [st for st in self.STAGES if st.name in ("contact", "bodies")]
+        if getattr(self, "bodies_enabled", False) and all(getattr(self, st.state) is not None for st in moved):
+            keep["bodies"] = [(st, getattr(self, st.state).clone()) for st in moved]
+        return keep
 
     def restore_state(self, keep):
         """Back to keep_state()'s moment: dof, dof_vel, then the clocks in the stages' order, so the k-th step from here sees the clock of the k-th step
@@ -128,3 +133,5 @@ class StageHost:
         self.dof_vel.copy_(keep["dof_vel"])
         for st, k in keep["clocks"]:
             self._clock_restore(st, k)
+        for st, whole in keep.get("bodies", ()):
+            getattr(self, st.state).copy_(whole)

@@ -169,8 +169,11 @@ class ContactMixin:
     def set_collider(self, index, point=None, normal=None, centre=None, radius=None, inside=None, velocity=None):
         """Changes collider `index` from the next substep on; what is left None keeps its value.  A plane takes point / normal, a sphere centre / radius /
         inside, both velocity.  A moving collider is scripted from the host with this, per frame, with `velocity` given for the relative velocity.
-        ValueError for an index without a collider, an argument of the other kind, or a value add_plane / add_sphere would refuse."""
+        ValueError for an index without a collider, an argument of the other kind, a value add_plane / add_sphere would refuse, or a slot that holds
+        a dynamic body (bodies.py): the ball moves on the device, so the mirror this call edits is stale — set_body changes it."""
         i = self._slot(index)
+        if self._is_body(i):
+            raise ValueError(f"contact: collider {i} is a dynamic body that moves on the device: use set_body, not set_collider")
         t, g = self._colliders[i]
         vel = g[7:10] if velocity is None else velocity
         if t == CONTACT_PLANE:
@@ -184,17 +187,23 @@ class ContactMixin:
         self._put_collider(i, c)
 
     def remove_collider(self, index):
-        """Empties the slot: the collider acts on no further substep, its index may be handed out again."""
-        self._put_collider(self._slot(index), None)
+        """Empties the slot: the collider acts on no further substep, its index may be handed out again.  A dynamic body in the slot (bodies.py) is
+        removed with it."""
+        i = self._slot(index)
+        self._drop_body(i)
+        self._put_collider(i, None)
 
     def clear_colliders(self):
         self._stage_state(STAGE, gpu=False)
         for i, c in enumerate(self._colliders):
             if c is not None:
+                self._drop_body(i)
                 self._put_collider(i, None)
 
     def contact_state_bytes(self):
-        """What the device state holds, packed from the mirror kept here (pack_contact_state): tests compare the device's bytes with it."""
+        """What the device state holds, packed from the mirror kept here (pack_contact_state): tests compare the device's bytes with it.  A slot that
+        holds a dynamic body (bodies.py) is the exception: on the device its p and v are the ball's motion, here what the host last gave it
+        (body_state() reads the device's)."""
         self._stage_state(STAGE, gpu=False)
         return pack_contact_state(1, self._contact_params, self._colliders)
 

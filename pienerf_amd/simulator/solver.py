@@ -17,9 +17,10 @@ import torch
 
 from .. import scene
 from .._lib import check, lib, ptr, stream_ptr
-from . import contact, drag, fields, gmls, pins, selfcontact
+from . import bodies, contact, drag, fields, gmls, pins, selfcontact
 from ._stage import StageHost, _null_ctx, _vec3, npfloat, torchfloat  # noqa: F401
 # every module-level name this file had before the stages moved into files of their own is still importable from here
+from .bodies import *  # noqa: F401,F403
 from .contact import *  # noqa: F401,F403
 from .drag import *  # noqa: F401,F403
 from .drag import _check_scale  # noqa: F401
@@ -31,13 +32,14 @@ from .selfcontact import *  # noqa: F401,F403
 CELL_CHUNK_IPS = 32   # points per chunk of the substep's cell form = pn_sim_cells_chunk_ips() (csrc/pn_sim_cells.h: PN_CELL_IPS), checked in _prepare_cells
 
 
-class Simulator(StageHost, DragMixin, PinsMixin, ContactMixin, FieldsMixin, SelfContactMixin):  # noqa: F405
+class Simulator(StageHost, DragMixin, PinsMixin, ContactMixin, BodiesMixin, FieldsMixin, SelfContactMixin):  # noqa: F405
     # The substep's stages, in the order stepforward() enqueues them.  Drag stands in front: it writes dof_f, not the right-hand side.  The others are
     # links of one chain, each writing (what the link before it wrote) + its own term into a buffer of its own, and the substep takes the last link in
     # its rhs_gravity slot: rhs_gravity -> pins -> contact -> fields -> self.  Pins lead because their term depends on time alone; contact, fields and
     # self-contact are evaluated from the dof / dof_vel the substep starts from, so their order changes the sum's rounding only — it is fixed so that
-    # a run's bits are.  initialize() allocates and precompute() builds tables in the same order.
-    STAGES = (drag.STAGE, pins.STAGE, contact.STAGE, fields.STAGE, selfcontact.STAGE)
+    # a run's bits are.  The rigid balls (bodies) stand behind contact and add nothing to the chain: they move collider slots, after contact has read
+    # them.  initialize() allocates and precompute() builds tables in the same order.
+    STAGES = (drag.STAGE, pins.STAGE, contact.STAGE, bodies.STAGE, fields.STAGE, selfcontact.STAGE)
 
     def __init__(self, dt=1e-2, iters=20, bbox=torch.tensor([1.0, 1.0, 1.0], dtype=torchfloat), kres=7, dx=1,
                  gravity=torch.tensor([0.0, -9.8, 0.0], dtype=torchfloat), stiff=1e5, base=torch.tensor([-0.5, -0.5, -0.5], dtype=torchfloat),
