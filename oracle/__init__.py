@@ -136,6 +136,18 @@ def warp_point(x, p_ori, p_def, F9, dF27, max_iter_num, IP_dx):
     return out, bool(rej)
 
 
+def warp_points(x, ips, p_ori, p_def, F_IP, dF_IP, max_iter_num, IP_dx):
+    """warp_point for n (point, IP id) pairs at once.  Returns (rest points [n, 3], rejected [n] bool, Newton updates run [n])."""
+    x, ips = _f32(x).reshape(-1, 3), _i32(ips).reshape(-1)
+    p_ori, p_def, F_IP, dF_IP = _f32(p_ori), _f32(p_def), _f32(F_IP), _f32(dF_IP)
+    n = x.shape[0]
+    assert ips.shape[0] == n and (n == 0 or (ips.min() >= 0 and ips.max() < p_ori.shape[0]))
+    out, rej, upd = np.empty((n, 3), np.float32), np.empty(n, np.int32), np.empty(n, np.int32)
+    lib().orc_warp_points(I(n), _p(x, F), _p(ips, I), _p(p_ori, F), _p(p_def, F), _p(F_IP, F), _p(dF_IP, F), I(max_iter_num), F(IP_dx), _p(out, F),
+                          _p(rej, I), _p(upd, I))
+    return out, rej.astype(bool), upd
+
+
 def march_rays(n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, bound, density_bitfield, Cc, H, near, far, align=-1, noises=None,
                dt_gamma=0.0, max_steps=1024):
     """raymarching.march_rays (raymarching.py:306-358 / raymarching.cu:703-824).  Returns zero-initialised xyzs, dirs, deltas."""

@@ -179,9 +179,11 @@ int find_closest_IPs(float x, float y, float z, const float* p_def, const Pig& p
 // Per-IP Newton inverse warp, raymarching.cu:1262-1324: solve F q + 1/2 (dF.q) q = q' for q = p - p_ori, q' = x - p_def,
 // starting at p = p_ori, at most max_iter_num updates, stopping when |dq|^2 < 1e-12 (checked after the update).
 // Returns true when the result is further than IP_dx (inf-norm) from p_ori — the caller then decrements n_IP.
-bool newton_warp(const float* x3, const float* pk, const float* pk_, const float* Fk, const float* dFk, int max_iter_num, float IP_dx, float* p) {
+// `updates` (optional, tests only): how many times p was updated.
+bool newton_warp(const float* x3, const float* pk, const float* pk_, const float* Fk, const float* dFk, int max_iter_num, float IP_dx, float* p,
+                 int* updates = nullptr) {
     p[0] = pk[0]; p[1] = pk[1]; p[2] = pk[2];
-    int num_itr = 0;
+    int num_itr = 0, n_upd = 0;
     const float q_[3] = {x3[0] - pk_[0], x3[1] - pk_[1], x3[2] - pk_[2]};
     while (num_itr < max_iter_num) {
         const float q[3] = {p[0] - pk[0], p[1] - pk[1], p[2] - pk[2]};
@@ -199,9 +201,11 @@ bool newton_warp(const float* x3, const float* pk, const float* pk_, const float
         p[0] -= dq[0];
         p[1] -= dq[1];
         p[2] -= dq[2];
+        n_upd++;
         if ((double)(dq[0] * dq[0] + dq[1] * dq[1] + dq[2] * dq[2]) < 1e-12) break;
         num_itr++;
     }
+    if (updates) *updates = n_upd;
     const float e0 = p[0] - pk[0], e1 = p[1] - pk[1], e2 = p[2] - pk[2];
     return fabsf(e0) > IP_dx || fabsf(e1) > IP_dx || fabsf(e2) > IP_dx;
 }
@@ -983,6 +987,16 @@ int orc_render_deformed(const float* rays_o, const float* rays_d, uint32_t N, co
 int orc_warp_point(const float* x3, const float* p_ori, const float* p_def, const float* F9, const float* dF27, int max_iter_num, float IP_dx,
                    float* out) {
     return newton_warp(x3, p_ori, p_def, F9, dF27, max_iter_num, IP_dx, out) ? 1 : 0;
+}
+
+// Test hook: the same warp for n (point, IP) pairs at once.  out[n * 3] = rest-space points, rej[n] = reject flags, updates[n] = Newton
+// updates each warp ran (1 .. max_iter_num).
+void orc_warp_points(int n, const float* x, const int* ip, const float* p_ori, const float* p_def, const float* F_IP, const float* dF_IP, int max_iter_num,
+                     float IP_dx, float* out, int* rej, int* updates) {
+    for (int i = 0; i < n; i++) {
+        const int k = ip[i];
+        rej[i] = newton_warp(x + 3 * i, p_ori + 3 * k, p_def + 3 * k, F_IP + 9 * k, dF_IP + 27 * k, max_iter_num, IP_dx, out + 3 * i, updates + i) ? 1 : 0;
+    }
 }
 
 int orc_num_threads(void) {

@@ -159,6 +159,38 @@ def test_march_quadratic_bending_equals_the_reference_kernel(mods, deformed_ip_s
     assert rate["xyzs"][1] < 2e-2 and rate["deltas"][0] < 0.05
 
 
+@pytest.mark.parametrize("num_seek_IP,max_iter_num,n_step", [(1, 1, 8), (3, 5, 8)])
+@pytest.mark.parametrize("name", ["crowded", "singular", "coincident"])
+def test_march_on_rough_states_equals_the_reference_kernel(mods, deformed_ip_state, small_opt, ckpt, name, num_seek_IP, max_iter_num, n_step):
+    """The reference's own kernel on the IP states of tests/march_states.py: candidate lists of more than a thousand entries with an exact distance
+    tie at every sample (crowded), det F == 0 / rank 1 / rank 2 / inverted F (singular), samples ON an IP with a second IP at the same place or at
+    d^2 = 2^-140 (coincident, n_step = 1).  What wins a tie and whether a denormal distance is kept are settled here by the reference's sequential
+    strict-'<' scan itself, not by a restatement of it."""
+    import march_states as ms
+    ref, fma, ours = mods
+    if name == "coincident":
+        ip, rays, facts = ms.coincident(deformed_ip_state, small_opt, ckpt)
+        m, alive, rays_t, n_step = ms.coincident_inputs(ip, rays), rays["alive"], rays["t"], 1
+    else:
+        ip, facts = ms.build(name, deformed_ip_state, small_opt)
+        m = ms.march_inputs(ip, W=96)
+        alive = np.nonzero(m["nears"] < 1e30)[0].astype(np.int32)
+        alive = np.concatenate([alive, np.arange(0, m["o"].shape[0], 97, dtype=np.int32)])
+        rays_t = m["nears"]
+    ms.check_facts(name, facts)
+    args = (m, ip, ckpt, alive, n_step, num_seek_IP, max_iter_num, False, np.zeros(6, np.float32), 0.0, 1024, np.zeros(len(alive), np.float32), rays_t)
+    r = _call_march(ref["raymarching"], *args)
+    g = _call_march(ours["raymarching"], *args)
+    f = _call_march(fma["raymarching"], *args)
+    emitted = int((r[2][:, 0] != 0).sum())
+    assert emitted >= (24 if name == "coincident" else 500)
+    for what, a, b in zip(("xyzs", "dirs", "deltas"), g, r):
+        assert bits_equal(a, b), f"{what}: {mismatch(a, b)}"
+    key = f"march_vs_fma[{name},seek{num_seek_IP},iter{max_iter_num},step{n_step}]"
+    REPORT[key] = dict({what: mismatch(a, b) for what, a, b in zip(("xyzs", "dirs", "deltas"), g, f)}, emitted=emitted)
+    print("vs default-contraction build:", REPORT[key])
+
+
 @pytest.mark.parametrize("background,num_seek_IP,n_step", [(False, 1, 6), (True, 1, 6), (True, 3, 2), (True, 2, 16)])
 def test_march_cut_mode_equals_the_reference_kernel(mods, deformed_ip_state, small_opt, ckpt, background, num_seek_IP, n_step):
     """--cut: bbox = +-bound, cut_bounds test with the reference's own `x < cut_bounds[3]` (raymarching.cu:1195-1210), static background samples,
