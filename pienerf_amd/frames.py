@@ -15,8 +15,8 @@ chip idle; rendering is embarrassingly parallel over frames.  So the step is sof
     it has long completed: the host never waits for the GPU in steady state and never leaves a lane empty while it enqueues.
 
 ``FramePipeline`` is that schedule and nothing else: every device action goes through a small *backend* (streams, events, and the five
-operations snapshot / substep / broadcast / render / copy-out).  ``pienerf_amd.harness`` supplies the HIP backend (torch streams, HIP
-graphs, RCCL); ``SimulatedBackend`` below executes the same enqueue sequence on CPU tensors with FIFO "streams" run in a randomised but
+operations snapshot / substep / broadcast / render / copy-out).  ``pienerf_amd.pipeline_hip`` supplies the HIP backend (torch streams, HIP
+graphs, RCCL; ``harness.capture_pipelined`` builds it); ``SimulatedBackend`` below executes the same enqueue sequence on CPU tensors with FIFO "streams" run in a randomised but
 dependency-respecting order and gloo broadcasts — what tests/test_frames_gloo.py uses to check, for 1-4 ranks, both placements and many
 more frames than snapshot slots, that no slot is overwritten before its readers ran and that every frame sees exactly its own state.
 """

@@ -19,6 +19,8 @@ import numpy as np
 import torch
 
 from . import scene
+from ._captured import Captured, LastFrame, refuse_form
+from ._lib import lib
 from .nerf.network import NeRFNetwork
 from .nerf.utils import get_rays
 from .simulator.solver import Simulator
@@ -38,10 +40,6 @@ def _capture(graph, **kw):
         if was:
             gc.enable()
 
-
-# pn_render_opts.throughput_trips: a trip marches in the throughput form (one lane per ray) when it has at least this many alive rays — 2048 waves,
-# two per SIMD (measured: trex option set, second trip of 246 k rays: 1 191 -> 1 321 steps/s; chair, second trip of 41 k rays: 1 650 -> 1 480)
-THROUGHPUT_FORM_MIN_RAYS = 131072
 
 class SimRenderHarness:
     def __init__(self, opt=None, cloud=None, ckpt=None, device="cuda", overlap_sim=True):
@@ -69,7 +67,16 @@ class SimRenderHarness:
         self.pose = scene.orbit_pose(o["radius"])
         self.intrinsics = scene.orbit_intrinsics(o["W"], o["H"], o["fovy"])
         self._pose_dev = None
+        self._graph = self._graph_done = None
+        self._captured_graph = self._captured_pipe = None   # Captured: what the step graph / the pipeline baked in, None until captured
+        self._pipe_form = None           # the pipeline's form by which step_pipelined() refuses (_captured.refuse_form)
+        self._last = None                # LastFrame: what drag(), move() and pick_drawn() read
+        self._collider_snapshot = None
+        self.graph_continued = 0
+        self._raw_streams = []
+        # _pipe and _pipe_backend stay unset until capture_pipelined(): bench.py asks hasattr(h, "_pipe_backend")
         self.overlap_sim = overlap_sim
+        self._sim_stream = None          # without overlap_sim: made by capture()
         if overlap_sim:
             self._sim_stream = torch.cuda.Stream(self.device)
             self._ip_ready = torch.cuda.Event()
@@ -91,6 +98,38 @@ class SimRenderHarness:
         """**vars(opt) as the reference passes it (trainer.py:318); renderer reads these by name."""
         return dict(self.opt)
 
+    @staticmethod
+    def _pose_tensor(pose):
+        """The [1, 4, 4] float32 host tensor of a camera pose (trainer.py:541)."""
+        return torch.from_numpy(np.asarray(pose, np.float32)).unsqueeze(0)
+
+    @staticmethod
+    def _frame_views(out, H, W):
+        """A render's flat image / depth / depth_0 as frames."""
+        return {"image": out["image"].reshape(-1, H, W, 3), "depth": out["depth"].reshape(-1, H, W), "depth_0": out["depth_0"].reshape(-1, H, W)}
+
+    def _render_frame(self, pose_dev, ip, kw, W, H, rays=None, out_buffers=None):
+        """One frame of every form: the model renders from the integration-point triple `ip` (None: what it holds) along the rays of the camera
+        `pose_dev` (`rays`: already built, where a step enqueues them in front of its substep), with the options `kw`.  Returns (rays, out)."""
+        m = self.model
+        if ip is not None:
+            m.p_def, m.IP_F, m.IP_dF = ip
+        if rays is None:
+            rays = get_rays(pose_dev, self.intrinsics, H, W, -1)
+        if m.point_overlay_key() is not None:
+            kw = dict(kw, point_pose=pose_dev)   # draw_points(): the camera this frame's rays come from
+        if out_buffers is not None:
+            kw = dict(kw, out_buffers=out_buffers)
+        with self._amp():
+            return rays, m.render_deformed(rays["rays_o"], rays["rays_d"], staged=True, bg_color=None, perturb=False, **kw)
+
+    def _now(self):
+        """The Captured record of the current state: what a replay is checked against, and what a capture keeps."""
+        return Captured(self.sim.enabled_stage_names(), self.model.collider_overlay_key(), self.model.point_overlay_key(), self._net_form_epoch())
+
+    def _refuse(self, form, now=None):
+        refuse_form(form, self._now() if now is None else now, self._shadows_set(), self.sim.bodies_enabled)
+
     @torch.no_grad()
     def step(self, pose=None, intrinsics=None, W=None, H=None, simulate=True, collect_stats=False, fused=True, render_kw=None):
         """render_kw: options of THIS render on top of self.opt (the pipeline's probes of a launch form pass theirs here instead of editing self.opt)."""
@@ -100,7 +139,7 @@ class SimRenderHarness:
         intrinsics = self.intrinsics if intrinsics is None else intrinsics
         key = np.asarray(pose, np.float32).tobytes()
         if self._pose_dev is None or self._pose_dev[0] != key:  # trainer.py:541 uploads the pose every frame; re-upload only when it changes
-            self._pose_dev = (key, torch.from_numpy(np.asarray(pose, np.float32)).unsqueeze(0).to(self.device))
+            self._pose_dev = (key, self._pose_tensor(pose).to(self.device))
         rays = get_rays(self._pose_dev[1], intrinsics, H, W, -1)
         m = self.model
         self._order_overlay_behind_setters()   # before this frame's substep goes onto the simulator's stream: the render still overlaps it
@@ -108,8 +147,7 @@ class SimRenderHarness:
             main = torch.cuda.current_stream(self.device)
             if self.overlap_sim:
                 main.wait_event(self._sim_done)            # the previous substep must have finished before dof is read
-            IP_pos, IP_F, IP_dF = self.sim.get_IP_info()
-            m.p_def, m.IP_F, m.IP_dF = IP_pos, IP_F, IP_dF
+            m.p_def, m.IP_F, m.IP_dF = self.sim.get_IP_info()
             self._snapshot_colliders()   # enable_bodies(): the balls this frame draws, as the substep below finds them
             if self.overlap_sim:
                 # the substep only feeds the NEXT frame (render lags sim by one frame, trainer.py:300-318), so it runs on a
@@ -125,46 +163,36 @@ class SimRenderHarness:
         kw = self.render_kwargs()
         kw.update(render_kw or {})
         kw["collect_stats"] = collect_stats
-        if m.point_overlay_key() is not None:
-            kw["point_pose"] = self._pose_dev[1]   # draw_points(): the camera this frame's rays come from
-        with self._amp():
-            if fused:
-                out = m.render_deformed(rays["rays_o"], rays["rays_d"], staged=True, bg_color=None, perturb=False, **kw)
-            else:
+        if fused:
+            _, out = self._render_frame(self._pose_dev[1], None, kw, W, H, rays=rays)   # (the state was installed with the substep, above)
+        else:
+            with self._amp():
                 out = m.rund_cuda_ops(rays["rays_o"], rays["rays_d"], bg_color=None, perturb=False, **kw)
-        if self.sim.drag_enabled:   # what drag() / move() unproject against (only then: without the drag nothing else is kept alive)
-            self._drag_frame = ("eager", out["depth_0"].reshape(H, W), m.p_def, pose, intrinsics)
-        res = {"image": out["image"].reshape(-1, H, W, 3), "depth": out["depth"].reshape(-1, H, W), "depth_0": out["depth_0"].reshape(-1, H, W),
-               "rays_o": rays["rays_o"], "rays_d": rays["rays_d"]}
+        res = dict(self._frame_views(out, H, W), rays_o=rays["rays_o"], rays_d=rays["rays_d"])
         res.update({k: out[k] for k in ("coverage", "collider_t", "shadow") if k in out})   # draw_colliders() / cast_shadows(): the overlay's own outputs
         if "point_id" in out:   # draw_points(): the drawn point per pixel, what pick_drawn() reads
             res.update(point_id=out["point_id"].reshape(-1, H, W), point_t=out["point_t"].reshape(-1, H, W))
-            self._points_frame = (res["point_id"], m.p_def)
+        if self.sim.drag_enabled:   # what drag() / move() unproject against (only then: without the drag nothing else is kept alive)
+            self._last = LastFrame("eager", out["depth_0"].reshape(H, W), m.p_def, pose, intrinsics, res.get("point_id"))
+        elif "point_id" in out:
+            self._last = (self._last or LastFrame())._replace(ip_pos=m.p_def, point_id=res["point_id"])
         return res
 
     # ------------------------------------------------------------------ whole step as one HIP graph
     def _step_body(self, n_trips, W, H):
         """get_rays -> get_IP_info -> { stepforward || render_deformed } with fork/join on the current stream (capturable)."""
-        m = self.model
         main = torch.cuda.current_stream(self.device)
         rays = get_rays(self._graph_pose, self.intrinsics, H, W, -1)
-        IP_pos, IP_F, IP_dF = self.sim.get_IP_info()
-        m.p_def, m.IP_F, m.IP_dF = IP_pos, IP_F, IP_dF
+        ip = self.sim.get_IP_info()
         self._snapshot_colliders()   # enable_bodies(): the balls this frame draws, as the substep below finds them
         self._sim_stream.wait_stream(main)
         with torch.cuda.stream(self._sim_stream):
             self.sim.stepforward()
-        kw = self.render_kwargs()
-        kw["async_trips"] = n_trips
-        if m.point_overlay_key() is not None:
-            kw["point_pose"] = self._graph_pose
-        with self._amp():
-            out = m.render_deformed(rays["rays_o"], rays["rays_d"], staged=True, bg_color=None, perturb=False, **kw)
+        _, out = self._render_frame(self._graph_pose, ip, dict(self.render_kwargs(), async_trips=n_trips), W, H, rays=rays)
         main.wait_stream(self._sim_stream)
         # every tensor the graph touches is returned (and so stays referenced): memory freed after capture would go back to the
         # graph's pool and could be handed out again
-        res = {"image": out["image"].reshape(-1, H, W, 3), "depth": out["depth"].reshape(-1, H, W), "depth_0": out["depth_0"].reshape(-1, H, W),
-               "weights_sum": out["weights_sum"], "rays_o": rays["rays_o"], "rays_d": rays["rays_d"], "_ip": (IP_pos, IP_F, IP_dF)}
+        res = dict(self._frame_views(out, H, W), weights_sum=out["weights_sum"], rays_o=rays["rays_o"], rays_d=rays["rays_d"], _ip=tuple(ip))
         res.update({k: out[k] for k in ("coverage", "collider_t", "shadow") if k in out})   # draw_colliders() / cast_shadows(): render_continue writes them again
         res.update({k: out[k] for k in ("point_id", "point_t") if k in out})   # draw_points(): flat [N], render_continue writes them again
         return res
@@ -175,9 +203,9 @@ class SimRenderHarness:
         baked in (the chair needs 5); step_graph() verifies afterwards that no ray was left alive."""
         o = self.opt
         W, H = W or o["W"], H or o["H"]
-        if not hasattr(self, "_sim_stream"):
+        if self._sim_stream is None:
             self._sim_stream = torch.cuda.Stream(self.device)
-        self._graph_pose = torch.from_numpy(np.asarray(self.pose, np.float32)).unsqueeze(0).to(self.device)
+        self._graph_pose = self._pose_tensor(self.pose).to(self.device)
         self._graph_pose_host = self.pose
         keep = self.sim.keep_state()
         warm = torch.cuda.Stream(self.device)
@@ -194,57 +222,14 @@ class SimRenderHarness:
         self.sim.reset_warm_start()       # ... and its SVD warm start: a replay from here has the bits of a simulator that never warmed up
         self._graph_trips = n_trips
         self._graph_done = None
-        self._graph_stages = self.sim.enabled_stage_names()   # a stage's launches (Simulator.STAGES) are in the graph or they are not
-        self._graph_overlay = self.model.collider_overlay_key()   # ... and the render's collider overlay, with its style (draw_colliders)
-        self._graph_points = self.model.point_overlay_key()   # ... and the point overlay's launch pair (draw_points)
-        self._graph_form_epoch = self._net_form_epoch()
+        self._captured_graph = self._now()
         return self
 
     def _net_form_epoch(self):
         """How often the fp32 network switched between its fp16 hi/lo and bf16 forms (include/pienerf_hip.h: pn_net_form_epoch).  The per-layer scales
         live in device memory and follow an in-place weight refresh; the form is baked into every captured launch."""
-        from ._lib import lib
         net = getattr(self.model, "_net", None)
         return int(lib().pn_net_form_epoch(net)) if net is not None else 0
-
-    def _check_net_form(self, captured, what):
-        if self._net_form_epoch() != captured:
-            raise RuntimeError(f"the network's weights were refreshed into another arithmetic form (pn_net_form) since {what} was captured: its graphs "
-                               f"hold the old form's kernels — capture again")
-
-    # a stage enabled after the capture: its state is device memory and is followed without a recapture, its launches must be in the graph
-    _STAGE_NOT_CAPTURED = {
-        "pins": "pin motion: {what} was captured before enable_pin_motion(), its substep ignores the pin motion: {again} again",
-        "contact": "contact: {what} was captured before enable_contact(), its substep ignores the colliders: {again} again",
-        "bodies": "bodies: {what} was captured before enable_bodies(), its substep does not move the balls: {again} again",
-        "fields": "fields: {what} was captured before enable_fields(), its substep ignores the force fields: {again} again",
-        "self": "self-contact: {what} was captured before enable_self_contact(), its substep ignores self-contact: {again} again",
-    }
-
-    def _check_stages_captured(self, captured, what, again):
-        now = self.sim.enabled_stage_names()
-        for name, msg in self._STAGE_NOT_CAPTURED.items():
-            if name in now and name not in captured:
-                raise RuntimeError(msg.format(what=what, again=again))
-
-    def _check_overlay_captured(self, captured, what, again):
-        """The colliders' state is device memory and is followed without a recapture; the overlay's launch, its style and t_max are in the graph."""
-        now = self.model.collider_overlay_key()
-        if now is not None and captured is None:
-            raise RuntimeError(f"colliders: {what} was captured before draw_colliders(), its frames do not draw the colliders: {again} again")
-        if now is not None and captured is not None and len(now) > len(captured):
-            raise RuntimeError(f"colliders: {what} was captured before cast_shadows(), its frames cast no shadows: {again} again")
-        if now != captured:
-            raise RuntimeError(f"colliders: the overlay (its state buffer, style, t_max or the shadows' light) changed since {what} was captured: {again} again")
-
-    def _check_points_captured(self, captured, what, again):
-        """Positions, pose and drag state are device memory and are followed without a recapture; the launch pair, its style and the intrinsics are in
-        the graph."""
-        now = self.model.point_overlay_key()
-        if now is not None and captured is None:
-            raise RuntimeError(f"points: {what} was captured before draw_points(), its frames do not draw the points: {again} again")
-        if now != captured:
-            raise RuntimeError(f"points: the point overlay (its style, intrinsics, values or drag state) changed since {what} was captured: {again} again")
 
     def draw_points(self, style=None, markers=True):
         """From the next frame on the renders draw the simulator's integration points into the finished picture — the reference's "render IPs"
@@ -261,13 +246,8 @@ class SimRenderHarness:
 
     def hide_points(self):
         self.model.clear_point_overlay()
-        self._points_frame = None
+        self._last = self._last and self._last._replace(point_id=None)
         return self
-
-    def _refuse_points_form(self, what):
-        if self.model.point_overlay_key() is not None:
-            raise RuntimeError(f"points: {what} does not draw the points (the other ranks / ray batches hold only a part of the frame the launch pair "
-                               "paints onto): step(), capture() and the single-process capture_pipelined() do; hide_points() first")
 
     def pick_drawn(self, x, y, point_id=None, ip_pos=None):
         """An exact pick through the picture: the integration point drawn at pixel (x, y) of the last frame (column x, row y) — that one value of the
@@ -277,12 +257,12 @@ class SimRenderHarness:
         if not self.sim.drag_enabled:
             raise RuntimeError("pick_drawn: call enable_drag() first (before capture() / capture_pipelined())")
         if point_id is None:
-            fr = getattr(self, "_points_frame", None)
-            if fr is None:
+            fr = self._last
+            if fr is None or fr.point_id is None:
                 raise RuntimeError("pick_drawn: no frame with the points drawn has been rendered yet (draw_points(), then a step)")
-            if getattr(self, "_drag_frame", ("",))[0] == "graph":
+            if fr.form == "graph":
                 self._check_previous_graph_frame()
-            point_id, ip_pos = fr[0], (fr[1] if ip_pos is None else ip_pos)
+            point_id, ip_pos = fr.point_id, (fr.ip_pos if ip_pos is None else ip_pos)
         if ip_pos is None:
             raise ValueError("pick_drawn: pass ip_pos, the integration-point positions the frame was rendered from")
         W, H = self.opt["W"], self.opt["H"]
@@ -318,15 +298,10 @@ class SimRenderHarness:
         if ov is None or not self.sim.bodies_enabled:
             return
         live = self.sim.collider_state()
-        if getattr(self, "_collider_snapshot", None) is None or ov[0] is not self._collider_snapshot:
+        if self._collider_snapshot is None or ov[0] is not self._collider_snapshot:
             self._collider_snapshot = live.clone()
             self.model.set_collider_overlay(self._collider_snapshot, ov[1], ov[2])
         self._collider_snapshot.copy_(live)
-
-    def _refuse_bodies_overlay_pipelined(self):
-        if self.sim.bodies_enabled and self.model.collider_overlay_key() is not None:
-            raise RuntimeError("bodies: the pipelined form draws the live collider state, which would show a ball sim_ahead frames in front of the object "
-                               "it touches; step() and capture() / step_graph() draw the balls; hide_colliders() first")
 
     def _order_overlay_behind_setters(self):
         """set_collider's one-thread launch runs on the simulator's force stream; a frame that draws the colliders reads the state on the render's
@@ -360,29 +335,18 @@ class SimRenderHarness:
     def _shadows_set(self):
         return getattr(self.model, "_shadows", None) is not None
 
-    def _refuse_overlay_form(self, what):
-        if self.model.collider_overlay_key() is not None:
-            raise RuntimeError(f"colliders: {what} does not draw the colliders (the other ranks / ray batches would need the collider state sent with "
-                               "the DOF snapshot): step(), capture() and the single-process capture_pipelined() do; hide_colliders() first")
-
-    def _refuse_shadows_pipelined(self):
-        if self._shadows_set():
-            raise RuntimeError("shadows: the pipelined form casts no shadows — each lane's workspace would need a shadow workspace and map of its own "
-                               "(the follow-up); step() and capture() / step_graph() do; hide_shadows() first")
-
     @torch.no_grad()
     def step_graph(self, pose=None):
         """Replays the captured step.  Outputs are static tensors (overwritten by the next replay); they are complete — including frames
         that needed more trips than were captured — after the NEXT call or ``finish_graph_frame()``."""
-        if getattr(self, "_graph", None) is None:
+        if self._graph is None:
             self.capture()
-        self._check_net_form(self._graph_form_epoch, "the step")
-        self._check_stages_captured(self._graph_stages, "the step graph", "capture()")
-        self._check_overlay_captured(self._graph_overlay, "the step graph", "capture()")
-        self._check_points_captured(getattr(self, "_graph_points", None), "the step graph", "capture()")
+        now, cap = self._now(), self._captured_graph
+        cap.check_substep(now, "graph")
+        cap.check_render(now, "graph")
         self._check_previous_graph_frame()
         if pose is not None:
-            self._graph_pose.copy_(torch.from_numpy(np.asarray(pose, np.float32)).unsqueeze(0))
+            self._graph_pose.copy_(self._pose_tensor(pose))
         self._order_overlay_behind_setters()
         self._graph.replay()
         self._graph_done = torch.cuda.Event()
@@ -390,14 +354,12 @@ class SimRenderHarness:
         self.frame += 1
         if pose is not None:
             self._graph_pose_host = pose
-        if "drag" in self._graph_stages:
-            g = self._graph_out
-            self._drag_frame = ("graph", g["depth_0"][0], g["_ip"][0], self._graph_pose_host, self.intrinsics)
+        g, pid = self._graph_out, self._graph_out.get("point_id")
+        if "drag" in cap.stages:
+            self._last = LastFrame("graph", g["depth_0"][0], g["_ip"][0], self._graph_pose_host, self.intrinsics, pid)
         else:
-            self._drag_frame = ("graph",)
-        if "point_id" in self._graph_out:
-            self._points_frame = (self._graph_out["point_id"], self._graph_out["_ip"][0])
-        return self._graph_out
+            self._last = LastFrame("graph", ip_pos=None if pid is None else g["_ip"][0], point_id=pid)
+        return g
 
     def finish_graph_frame(self):
         """Waits for the last replayed step and completes it; returns its outputs."""
@@ -407,7 +369,7 @@ class SimRenderHarness:
     def _check_previous_graph_frame(self):
         """The captured step bakes in a trip count; a frame that still had rays alive after them is finished here with further trips (the
         reference's loop just keeps going, renderer.py:836-891) before its outputs are handed on."""
-        if getattr(self, "_graph_done", None) is not None:
+        if self._graph_done is not None:
             self._graph_done.synchronize()  # normally long complete: the host only ever runs one frame ahead
             st = self.model.render_status(synchronize=False)
             alive = st["alive_at_exit"]
@@ -421,20 +383,9 @@ class SimRenderHarness:
                     self.model.p_def, self.model.IP_F, self.model.IP_dF = g["_ip"]   # the point overlay paints the state this frame was rendered from
                 with self._amp():
                     self.model.render_continue(0, g["rays_o"], g["rays_d"], g, bg_color=None, **dict(self.render_kwargs(), point_pose=self._graph_pose))
-                self.graph_continued = getattr(self, "graph_continued", 0) + 1
+                self.graph_continued += 1
 
     # ------------------------------------------------------------------ several frames in flight (one GPU, or frame-parallel over a node)
-    def _cu_masked_stream(self, first_cu, n_cu, invert):
-        import ctypes
-
-        from ._lib import check, lib
-        total = lib().pn_device_cu_count()
-        h = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            check(lib().pn_stream_create_cu_mask(total, first_cu, n_cu, int(invert), ctypes.byref(h)), "stream_create_cu_mask")
-        self._raw_streams = getattr(self, "_raw_streams", []) + [h.value]
-        return torch.cuda.ExternalStream(h.value, device=self.device)
-
     @torch.no_grad()
     def capture_pipelined(self, lanes=2, n_trips=8, W=None, H=None, sim_ahead=None, depth=2, sim_priority=0, sim_cus=0, copy_out=True, group=None,
                           frame_parallel=False, sim_owner=0, dedicated_sim=None, on_retire=None, copy_on="host", _probe_no_substep=False, _time_trips=False,
@@ -459,15 +410,10 @@ class SimRenderHarness:
         update_force() acts from the next substep that is enqueued (it is ordered on the simulator's stream)."""
         import torch.distributed as dist
 
-        from .frames import FramePipeline
-        if frame_parallel:
-            self._refuse_overlay_form("the frame-parallel pipeline")
-            self._refuse_points_form("the frame-parallel pipeline")
-        if (render_kw or {}).get("ray_batch"):
-            self._refuse_overlay_form("the staged form")
-            self._refuse_points_form("the staged form")
-        self._refuse_shadows_pipelined()
-        self._refuse_bodies_overlay_pipelined()
+        from .frames import FramePipeline, dedicated_sim_default
+        from .pipeline_hip import _HipBackend
+        form = "frame_parallel" if frame_parallel else "staged" if (render_kw or {}).get("ray_batch") else "pipelined"
+        self._refuse(form)
         o = self.opt
         W, H = W or o["W"], H or o["H"]
         on = bool(frame_parallel) and dist.is_available() and dist.is_initialized()
@@ -476,7 +422,6 @@ class SimRenderHarness:
         if n_trips is None:  # calibrate: the trips one eager frame needs from the current state and pose, plus a margin
             self.step(simulate=False, collect_stats=True, W=W, H=H)
             n_trips = int(self.model.last_stats["trips"]) + 2  # every captured trip costs five launches whether it has rays or not
-        from .frames import dedicated_sim_default
         if (world > 1 and (dedicated_sim_default(world) if dedicated_sim is None else bool(dedicated_sim)) and rank == sim_owner
                 and dist.get_backend(group) == "nccl" and os.environ.get("PN_SIM_COOP", "") == "1"):
             # this GPU only simulates: with PN_SIM_COOP=1 the substep's local/global iterations run as one persistent kernel on (almost) every CU
@@ -491,13 +436,10 @@ class SimRenderHarness:
                                    sim_owner=sim_owner, dedicated_sim=dedicated_sim, copy_out=copy_out, on_retire=on_retire,
                                    force_collectives=bool(_force_collectives) and on, sim_on_lanes=sim_on_lanes)
         self.sim.force_hooks = (self._pipe.before_force, self._pipe.after_force) if self._pipe.sim_on_lanes else None
-        self._pipe_stages = self.sim.enabled_stage_names()
-        self._pipe_overlay = self.model.collider_overlay_key()
-        self._pipe_points = self.model.point_overlay_key()
-        self._pipe_single = not frame_parallel and not (render_kw or {}).get("ray_batch")
-        self._drag_frame = ("pipelined",)
+        self._captured_pipe = self._now()
+        self._pipe_form = "pipelined" if form == "pipelined" else "parallel_or_staged"   # what step_pipelined() refuses by
+        self._last = LastFrame("pipelined")   # drag() and pick_drawn() are handed the retired frame's depth_0 / point_id
         self._pipe_backend = be
-        self._pipe_form_epoch = self._net_form_epoch()
         self.model._in_flight = lambda pipe=self._pipe: sum(f is not None for f in pipe.pending)  # weight refreshes need a drained pipeline (network._net_handle)
         return self
 
@@ -507,15 +449,10 @@ class SimRenderHarness:
 
     @torch.no_grad()
     def step_pipelined(self, pose=None):
-        self._check_net_form(self._pipe_form_epoch, "the pipeline")
-        self._check_stages_captured(self._pipe_stages, "the pipeline", "capture_pipelined()")
-        if not getattr(self, "_pipe_single", True):
-            self._refuse_overlay_form("the frame-parallel / staged pipeline")
-            self._refuse_points_form("the frame-parallel / staged pipeline")
-        self._refuse_shadows_pipelined()
-        self._refuse_bodies_overlay_pipelined()
-        self._check_overlay_captured(getattr(self, "_pipe_overlay", None), "the pipeline", "capture_pipelined()")
-        self._check_points_captured(getattr(self, "_pipe_points", None), "the pipeline", "capture_pipelined()")
+        now, cap = self._now(), self._captured_pipe
+        cap.check_substep(now, "pipe")
+        self._refuse(self._pipe_form, now)
+        cap.check_render(now, "pipe")
         out = self._pipe.step(pose)
         self.frame = self._pipe.frame
         return out
@@ -538,9 +475,8 @@ class SimRenderHarness:
     def wait_frame_copies(self):
         """Pipelined mode: host-waits for the device AND for the copier thread's frame copies (which are on no stream)."""
         torch.cuda.synchronize(self.device)
-        be = getattr(self, "_pipe_backend", None)
-        if be is not None and hasattr(be, "wait_copies"):
-            be.wait_copies()
+        if hasattr(self, "_pipe_backend"):   # unset until capture_pipelined(), see __init__: bench.py's barrier comes here in every form
+            self._pipe_backend.wait_copies()
 
     @torch.no_grad()
     def verify_last_frame(self):
@@ -557,16 +493,11 @@ class SimRenderHarness:
         res = be.result(ws)
         keep = (m.p_def, m.IP_F, m.IP_dF)
         try:
-            m.p_def, m.IP_F, m.IP_dF = be.ip[ws]
-            rays = get_rays(be.pose_dev[ws], self.intrinsics, be.H, be.W, -1)
             kw = dict(self.render_kwargs())
             kw.pop("ray_batch", None)
             if be.kw.get("ray_batch"):
                 kw["ray_batch"] = be.kw["ray_batch"]   # batches keep their own trip schedules: part of what the frame IS, not of how it is launched
-            if m.point_overlay_key() is not None:
-                kw["point_pose"] = be.pose_dev[ws]
-            with self._amp():
-                out = m.render_deformed(rays["rays_o"], rays["rays_d"], staged=True, bg_color=None, perturb=False, **kw)
+            _, out = self._render_frame(be.pose_dev[ws], be.ip[ws], kw, be.W, be.H)
             torch.cuda.synchronize(self.device)
             worst, ok = 0.0, True
             for k in ("image", "depth_0"):
@@ -593,12 +524,11 @@ class SimRenderHarness:
         (20 B x N / world per rank over RCCL) gives every rank the whole frame.  Unlike the frame-parallel pipeline, whose throughput is
         capped by the time-sequential simulator, this divides the render LATENCY of a frame by the rank count.  Launches are eager."""
         from .frames import TileParallel
-        self._refuse_overlay_form("the tile-parallel form")
-        self._refuse_points_form("the tile-parallel form")
+        self._refuse("tile_parallel")
         o, m, dev = self.opt, self.model, self.device
         W, H = W or o["W"], H or o["H"]
         ip = tuple(torch.empty((self.sim.n_IP, c), dtype=torch.float32, device=dev) for c in (3, 9, 27))
-        self._tile_pose = torch.from_numpy(np.asarray(self.pose, np.float32)).unsqueeze(0).to(dev)
+        self._tile_pose = self._pose_tensor(self.pose).to(dev)
 
         def render_subset(idx):
             rays = get_rays(self._tile_pose, self.intrinsics, H, W, -1)
@@ -620,10 +550,9 @@ class SimRenderHarness:
     @torch.no_grad()
     def step_tile_parallel(self, pose=None):
         """One sim+render step; every rank gets the full frame: {'image' [1,H,W,3], 'depth' [1,H,W], 'depth_0' [1,H,W]} on the device."""
-        self._refuse_overlay_form("the tile-parallel form")
-        self._refuse_points_form("the tile-parallel form")
+        self._refuse("tile_parallel")
         if pose is not None:
-            self._tile_pose.copy_(torch.from_numpy(np.asarray(pose, np.float32)).view(1, 4, 4).to(self.device))
+            self._tile_pose.copy_(self._pose_tensor(pose).to(self.device))
         full = self._tile.step()
         W, H = self._tile_WH
         self.frame += 1
@@ -640,13 +569,6 @@ class SimRenderHarness:
         rk = dict(kw.pop("render_kw", None) or {}, ray_batch=int(batch or self.opt.get("max_ray_batch", 4096)))  # this pipeline's renders only: self.opt stays as it was
         return self.capture_pipelined(render_kw=rk, **kw)
 
-    # names of rounds 1-2 (one captured launch chain per batch), kept as aliases of the pipeline's calls
-    def step_staged(self, pose=None):
-        return self.step_pipelined(pose)
-
-    def finish_staged(self):
-        return self.drain_pipeline()
-
     # ------------------------------------------------------------------ the GUI's mouse drag (gui.py:556-586, :833-841)
     def enable_drag(self, scale=None):
         """Simulator.enable_drag: every substep from now on gets the GUI's spring force toward the cursor, computed on the device from the state that
@@ -657,18 +579,18 @@ class SimRenderHarness:
     def _drag_check(self):
         if not self.sim.drag_enabled:
             raise RuntimeError("drag: call enable_drag() first (before capture() / capture_pipelined())")
-        mode = getattr(self, "_drag_frame", None)
-        if mode is None:
+        fr = self._last
+        if fr is None or fr.form is None:
             raise RuntimeError("drag: no frame has been rendered yet (the cursor is unprojected against the last frame's depth_0)")
-        if mode[0] == "graph" and not self._graph_drag:
+        if fr.form == "graph" and "drag" not in self._captured_graph.stages:
             raise RuntimeError("drag: the step graph was captured before enable_drag(), its substep ignores the drag state: capture() again")
-        if mode[0] == "pipelined" and not self._pipe_drag:
+        if fr.form == "pipelined" and "drag" not in self._captured_pipe.stages:
             raise RuntimeError("drag: the pipeline was captured before enable_drag(), its substep ignores the drag state: capture_pipelined() again")
-        return mode
+        return fr
 
     def _drag_inputs(self, depth0, ip_pos, pick):
-        mode = self._drag_check()
-        if mode[0] == "pipelined":
+        fr = self._drag_check()
+        if fr.form == "pipelined":
             # the caller hands in the last RETIRED frame's depth_0: the cursor is then unprojected against an image `lanes * depth` frames older than
             # the state the next substep reads — inherent to the pipeline.  The pick searches the IPs of the simulator's newest state.
             if depth0 is None:
@@ -678,9 +600,9 @@ class SimRenderHarness:
                 with self.sim._on_force_stream():
                     ip_pos = self.sim.get_IP_info()[0]
             return depth0, ip_pos, self.pose, self.intrinsics
-        if mode[0] == "graph":
+        if fr.form == "graph":
             self._check_previous_graph_frame()   # a frame left with rays alive is finished before its depth_0 is read
-        return (mode[1] if depth0 is None else depth0), (mode[2] if ip_pos is None else ip_pos), mode[3], mode[4]
+        return (fr.depth_0 if depth0 is None else depth0), (fr.ip_pos if ip_pos is None else ip_pos), fr.pose, fr.intrinsics
 
     def drag(self, x, y, depth0=None, ip_pos=None):
         """A ctrl-click at image pixel (x, y) (gui.py:833-841): picks the integration point nearest to the unprojected cursor among the IP positions
@@ -702,348 +624,3 @@ class SimRenderHarness:
     def to_host(self, out):
         """The reference's device->host boundary (trainer.py:589-592)."""
         return {k: out[k][0].detach().cpu().numpy() for k in ("image", "depth", "depth_0")}
-
-
-# h._graph_fields, h._pipe_drag, ...: whether the stage's launches are in the step graph / the pipeline's substep graph (False before a capture)
-for _form in ("_graph", "_pipe"):
-    for _st in Simulator.STAGES:
-        setattr(SimRenderHarness, f"{_form}_{_st.name}", property(lambda self, _f=_form + "_stages", _n=_st.name: _n in getattr(self, _f, ())))
-
-
-class _HipStream:
-    def __init__(self, s):
-        self.s = s
-
-    def wait(self, ev):
-        self.s.wait_event(ev.e)
-
-
-class _HostCopyStream:
-    """Stands where frames.FramePipeline expects the stream of the frame copies when they are done by the library's host-side copier
-    (pn_copier, copy_on="host"): `wait(event)` names the event the next copy has to follow, `_HipBackend.copy_out` submits the copy behind it,
-    an event `recorded` here carries the copy's ticket and can only be waited for by the host (which is all the pipeline does with it)."""
-
-    def __init__(self, backend):
-        self.backend, self.after, self.ticket = backend, None, None
-
-    def wait(self, ev):
-        self.after = ev
-
-
-class _HipEvent:
-    def __init__(self):
-        self.e = torch.cuda.Event()
-        self.copy = None  # (copier handle, ticket) when the event marks the end of a host-side frame copy
-
-    def record(self, stream):
-        if isinstance(stream, _HostCopyStream):
-            self.copy = (stream.backend.copier, stream.ticket)
-        else:
-            self.copy = None
-            self.e.record(stream.s)
-
-    def host_wait(self):
-        if self.copy is not None:
-            from ._lib import check, lib
-            check(lib().pn_copier_wait(self.copy[0], self.copy[1]), "copier_wait")
-        else:
-            self.e.synchronize()
-
-
-class _HipBackend:
-    """The device side of frames.FramePipeline on one MI355X: torch streams and events, the substep and one render per workspace captured
-    as HIP graphs, RCCL broadcasts of the dof snapshots, D2H into pinned buffers."""
-
-    def __init__(self, h, lanes, depth, n_trips, W, H, sim_priority, sim_cus, copy_out, group, src, probe_no_substep, time_trips=False, copy_on="host",
-                 render_kw=None, distributed=False):
-        # stream of the per-frame D2H.  gfx950 runs 4 hardware queues concurrently and time-slices beyond that (DESIGN.md 4): with 3 render lanes +
-        # the simulator stream a copy stream of its own is a fifth busy queue (measured: 808 steps/s against 1016 with the copy on the frame's own
-        # lane).  "copy": a stream of its own; "lane": the frame's render stream; "sim": the simulator stream; "host": no stream at all — the
-        # library's copier thread waits for the render's event and hands the copy to the HSA runtime (SDMA), see csrc/pn_copier.hip
-        self.copy_on = copy_on
-        self.copier = None
-        if copy_on == "host" and copy_out:
-            import ctypes
-
-            from ._lib import check, lib
-            hc = ctypes.c_void_p()
-            check(lib().pn_copier_create(ctypes.byref(hc)), "copier_create")
-            self.copier = hc
-        self.h, self.lanes, self.depth, self.trips, self.W, self.H, self.group, self.src = h, lanes, depth, n_trips, W, H, group, src
-        dev, m, sim = h.device, h.model, h.sim
-        self.continued = 0
-        if sim_cus > 0:
-            # compute-unit partition: the substep's chain of small dependent launches gets `sim_cus` CUs of its own (spread over the XCDs),
-            # the render lanes the rest, so a substep never waits for a render wave to release registers
-            self._streams = {"sim": h._cu_masked_stream(0, sim_cus, invert=False)}
-            lane_streams = [h._cu_masked_stream(0, sim_cus, invert=True) for _ in range(lanes)]
-        elif sim_cus < 0:
-            # the converse: the render lanes stay off -sim_cus CUs, the simulator may use every CU — its launches always find those free, and whatever else is
-            self._streams = {"sim": torch.cuda.Stream(dev, priority=sim_priority)}
-            lane_streams = [h._cu_masked_stream(0, -sim_cus, invert=True) for _ in range(lanes)]
-        else:
-            self._streams = {"sim": torch.cuda.Stream(dev, priority=sim_priority)}
-            lane_streams = [torch.cuda.Stream(dev) for _ in range(lanes)]
-        for i, s in enumerate(lane_streams):
-            self._streams[f"lane{i}"] = s
-        self._streams["comm"], self._streams["copy"] = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
-        sim.force_stream = self._streams["sim"]   # a force change is enqueued between two substeps of the simulator stream
-        self.snap = {}
-        n_ws, n_IP = lanes * depth, sim.n_IP
-        self.consumer_done = [None] * n_ws   # per workspace: the event behind what on_retire enqueued on its stream (consumer_fence)
-        kw = dict(h.render_kwargs(), async_trips=n_trips)
-        kw.update(render_kw or {})  # options of THIS pipeline's renders (capture_staged: ray_batch)
-        # several frames in flight: the first trip's march pass in its throughput form (pn_render_opts.throughput: one lane per ray, no speculative
-        # evaluation; the same samples bit for bit, +8 % steps/s with three lanes) — with one lane the frame's own latency is what counts
-        kw.setdefault("march_throughput", 64 if lanes > 1 else 0)
-        # ... and each frame's fused launch (pn_render_opts.fused_from) on half of the CUs: the launches of the frames in flight run side by side and the
-        # other kernels find CUs with free LDS (pn_render_opts.fused_grid; three lanes on the chair: 1 721 -> 1 937 steps/s)
-        if lanes > 1:
-            cus = torch.cuda.get_device_properties(dev).multi_processor_count
-            kw.setdefault("fused_grid", max(cus * 5 // 8 if lanes == 2 else cus // 2, 1))   # (two lanes, whole-frame launches: 128 / 160 / 192 workgroups: 1 717 / 1 776 / 1 689 steps/s)
-        self.kw = kw
-        if "fused_from" not in kw:
-            # pn_render_opts.fused_from: the loop trips from the first one with n_step == 8 on (n_alive <= N / 8: it stays 8 for the rest of the frame) run
-            # as ONE persistent launch (csrc/pn_trips_fused.h) — read off the trip records of a blocking frame from the current state and pose.  A later
-            # frame that still has more rays alive at that trip is finished when it is retired (frames.FramePipeline: continue), only slower
-            h.step(simulate=False, collect_stats=True, W=W, H=H)
-            recs = m.trip_records(slot=0, max_trips=64)
-            kw["fused_from"] = next((i for i, r in enumerate(recs) if i >= 1 and r[1] == 8), -1) if not kw.get("ray_batch") else -1
-        if "fused_whole" not in kw:
-            # pn_render_opts.fused_whole: the frame's first trip in that launch too (where at most N / 8 rays have anything to march: the blocking frame
-            # below tries it and reports the trip at which the fused launch took over).  Measured on the chair: better with two frames in flight
-            # (1 700-1 740 against 1 560 steps/s), worse with three (1 730 against 1 930) or one at a time — include/pienerf_hip.h
-            whole = lanes == 2 and kw["fused_from"] == 1
-            if whole:
-                h.step(simulate=False, collect_stats=True, W=W, H=H, render_kw=dict(kw, fused_whole=True, fused_from=0, async_trips=0))
-                whole = m.fused_clocks(slot=0)["first_trip"] == 0
-            kw["fused_whole"] = bool(whole)
-            if whole:
-                kw["fused_from"] = 0
-        if "fused_fold" not in kw:
-            # pn_render_opts.fused_fold: the first trip's network, composite and compaction inside the fused launch (its march stays launches of its own): four
-            # launches fewer on a lane's chain.  Where the blocking frame below finds it applicable (at most N / 8 rays with a sample on the first trip)
-            # (measured on the chair, alternating runs on one box: three lanes 1 960 against 1 925 steps/s, --steps 20: 1 801 against 1 790; one frame at a
-            # time the launch with the first trip's tiles in front of its rounds is longer than what it replaces, 0.884 against 0.859 ms per step)
-            # — that against the launch drawing its rays in list order.  Drawing each workgroup's longest packets first (pn_render_opts.fused_order, the
-            # default) shortens the launch whose rays come from the alive list by 5-6 %, and does nothing for the folded one, whose rays are listed while it
-            # runs: three lanes 1 503-1 508 against 1 483-1 486 steps/s on one box (EXPERIMENTS.md, "After round 6").  So: folded only in list order
-            ordered = kw.get("fused_order") is None or bool(kw.get("fused_order"))
-            fold = lanes >= 3 and (not kw.get("fused_whole")) and kw["fused_from"] == 1 and not ordered
-            if fold:
-                h.step(simulate=False, collect_stats=True, W=W, H=H, render_kw=dict(kw, fused_fold=True, async_trips=0))
-                fold = m.fused_clocks(slot=0)["mode"] == 2
-            kw["fused_fold"] = bool(fold)
-        if distributed:
-            # every rank of a frame-parallel job runs the launch form rank `src` picked (each probed its own warm-up frame: the same state and pose, but
-            # nothing guarantees the same answer at a threshold) — round-4 advisor; gated on the job being distributed, NOT on `group`: the default
-            # process group is group=None (round-5 advisor: with `if group is not None` this never ran in a real job)
-            from .frames import agree_on_launch_form
-            agree_on_launch_form(kw, src=src, group=group, device=dev)
-        pose0 = torch.from_numpy(np.asarray(h.pose, np.float32)).unsqueeze(0)
-        self.pose_dev = [pose0.to(dev) for _ in range(n_ws)]
-        self.pose_pin = [pose0.clone().pin_memory() for _ in range(n_ws)]
-        self.pose_key = [pose0.numpy().tobytes()] * n_ws
-        self.ip = [tuple(torch.empty((n_IP, c), dtype=torch.float32, device=dev) for c in (3, 9, 27)) for _ in range(n_ws)]
-        keep = sim.keep_state()
-        main = torch.cuda.current_stream(dev)
-        for ws in range(n_ws):  # warm-up of every workspace outside capture (creates the pn_frame workspaces, the fp16 tables, ...)
-            s = self._streams[f"lane{ws // depth}"]
-            s.wait_stream(main)
-            with torch.cuda.stream(s):
-                for _ in range(2):
-                    sim.get_IP_info(out=self.ip[ws])
-                    sim.stepforward()
-                    m.p_def, m.IP_F, m.IP_dF = self.ip[ws]
-                    rays = get_rays(self.pose_dev[ws], h.intrinsics, H, W, -1)
-                    with h._amp():
-                        m.render_deformed(rays["rays_o"], rays["rays_d"], staged=True, bg_color=None, perturb=False, **self._ws_kw(ws))
-            torch.cuda.synchronize(dev)
-            if ws == 0 and kw.get("march_throughput") and "march_throughput_trips" not in kw:
-                # the throughput form for every leading trip that still has rays enough to fill the GPU with ONE lane per ray (the trex option set's
-                # second trip: 246 k rays x 3 samples; the chair's: 41 k x 8, faster in the windows) — from this warm-up frame's trip records; the
-                # samples do not depend on the form, so a scene that changes later only loses speed
-                n_lpr = 1
-                for rec in m.trip_records(slot=0)[1:]:
-                    if rec[0] < THROUGHPUT_FORM_MIN_RAYS:
-                        break
-                    n_lpr += 1
-                kw["march_throughput_trips"] = n_lpr
-        # capture_error_mode="thread_local": with a process group alive, RCCL's watchdog thread queries events while we capture;
-        # in the default "global" mode any HIP call from another thread invalidates the capture
-        self.sim_graph = torch.cuda.CUDAGraph()
-        with _capture(self.sim_graph, stream=self._streams["sim"]):
-            if not probe_no_substep:
-                sim.stepforward()
-            else:
-                sim.dof_vel.mul_(1.0)
-        self.graph, self.rays, self.out, self.host, self.packed = [], [], [], [], []
-        N = W * H
-        for ws in range(n_ws):
-            s = self._streams[f"lane{ws // depth}"]
-            m.p_def, m.IP_F, m.IP_dF = self.ip[ws]  # the render graph of this workspace reads its own IP buffers
-            if time_trips:  # measurement (bench.py): time stamps around each trip's march / network launches become nodes of the captured graph
-                m.march_counters(2, slot=ws)
-            # image | depth | depth_0 packed in one device buffer -> ONE device-to-host copy per frame (20 B per pixel, trainer.py:589-592)
-            pk = torch.empty(N * 5, dtype=torch.float32, device=dev)
-            ob = {"image": pk[:3 * N].view(N, 3), "depth": pk[3 * N:4 * N], "depth_0": pk[4 * N:], "weights_sum": torch.empty(N, dtype=torch.float32, device=dev)}
-            g = torch.cuda.CUDAGraph()
-            with _capture(g, stream=s):
-                rays = get_rays(self.pose_dev[ws], h.intrinsics, H, W, -1)
-                with h._amp():
-                    out = m.render_deformed(rays["rays_o"], rays["rays_d"], staged=True, bg_color=None, perturb=False, out_buffers=ob, **self._ws_kw(ws))
-            self.graph.append(g)
-            # every tensor the graphs touch stays referenced: a tensor freed after capture goes back to the graph's memory pool
-            self.rays.append(rays)
-            self.out.append(out)
-            self.packed.append(pk)
-            # two pinned sets per workspace, used alternately: the arrays handed out when a frame is retired stay valid until the workspace has
-            # been through another whole frame (the next frame's D2H goes into the other set)
-            self.host.append([torch.empty(N * 5, dtype=torch.float32).pin_memory() for _ in range(2)] if copy_out else None)
-        self.host_gen = [0] * n_ws
-        torch.cuda.synchronize(dev)
-        if self.copier is not None:
-            # the first SDMA copy into a pinned buffer maps it for the engine (milliseconds): once per buffer here, not inside the pipeline's first frames
-            import ctypes
-
-            from ._lib import check, lib
-            for ws in range(n_ws):
-                for hb in self.host[ws]:
-                    t = ctypes.c_uint64()
-                    check(lib().pn_copier_submit(self.copier, ctypes.c_void_p(hb.data_ptr()), ctypes.c_void_p(self.packed[ws].data_ptr()),
-                                                 hb.numel() * hb.element_size(), None, ctypes.byref(t)), "copier_submit")
-                    check(lib().pn_copier_wait(self.copier, t.value), "copier_wait")
-        sim.restore_state(keep)    # warm-up advanced the simulator and its stages' clocks; capture itself executes nothing
-        sim.reset_warm_start()     # ... and its SVD warm start: a replay from here has the bits of a simulator that never warmed up
-        torch.cuda.synchronize(dev)
-
-    def _ws_kw(self, ws):
-        """The render options of workspace `ws`: its frame workspace and, with draw_points(), its own camera for the point overlay."""
-        kw = dict(self.kw, frame_slot=ws)
-        if self.h.model.point_overlay_key() is not None:
-            kw["point_pose"] = self.pose_dev[ws]
-        return kw
-
-    # ---- streams / events
-    def stream(self, name):
-        if name == "copy" and self.copier is not None:
-            return _HostCopyStream(self)
-        return _HipStream(self._streams[name])
-
-    def __del__(self):
-        if getattr(self, "copier", None) is not None:
-            try:
-                from ._lib import lib
-                lib().pn_copier_destroy(self.copier)
-            except Exception:  # noqa: BLE001 — interpreter shutdown: the import machinery is gone, the process is about to end anyway
-                pass
-            self.copier = None
-
-    def event(self):
-        return _HipEvent()
-
-    def _snap(self, slot):
-        if slot not in self.snap:
-            self.snap[slot] = torch.empty_like(self.h.sim.dof)
-        return self.snap[slot]
-
-    # ---- device operations
-    def snapshot(self, s, slot):
-        with torch.cuda.stream(s.s):
-            self._snap(slot).copy_(self.h.sim.dof)
-
-    def substep(self, s):
-        with torch.cuda.stream(s.s):
-            self.sim_graph.replay()
-
-    def broadcast(self, s, slot, src):
-        import torch.distributed as dist
-        with torch.cuda.stream(s.s):
-            dist.broadcast(self._snap(slot), src=self.src, group=self.group)
-
-    def consumer_fence(self, ws):
-        """After on_retire(frame, result): whatever the consumer enqueued on its current stream (a copy of the device tensors) is ordered before
-        the workspace's next render overwrites them."""
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self.h.device))
-        self.consumer_done[ws] = ev
-
-    def render(self, s, frame, ws, slot, pose):
-        with torch.cuda.stream(s.s):
-            if self.consumer_done[ws] is not None:
-                s.s.wait_event(self.consumer_done[ws])
-                self.consumer_done[ws] = None
-            # the camera of this frame (trainer.py:541): the given pose, else the harness's current one.  Every workspace keeps its own device
-            # copy (the graph reads it), so it is uploaded whenever it differs from what THIS workspace last rendered — staged in pinned memory,
-            # in stream order before the graph reads it
-            p = np.ascontiguousarray(self.h.pose if pose is None else pose, dtype=np.float32).reshape(1, 4, 4)
-            key = p.tobytes()
-            if self.pose_key[ws] != key:
-                self.pose_key[ws] = key
-                self.pose_pin[ws].copy_(torch.from_numpy(p))
-                self.pose_dev[ws].copy_(self.pose_pin[ws], non_blocking=True)
-            self.h.sim.get_IP_info(dof=self._snap(slot), out=self.ip[ws])
-            self.graph[ws].replay()
-
-    def copy_out(self, s, ws, same_buffer=False):
-        if not same_buffer:
-            self.host_gen[ws] ^= 1
-        dst, src = self.host[ws][self.host_gen[ws]], self.packed[ws]
-        if isinstance(s, _HostCopyStream):
-            import ctypes
-
-            from ._lib import check, lib
-            t = ctypes.c_uint64()
-            after = ctypes.c_void_p(s.after.e.cuda_event) if s.after is not None else None
-            check(lib().pn_copier_submit(self.copier, ctypes.c_void_p(dst.data_ptr()), ctypes.c_void_p(src.data_ptr()), src.numel() * src.element_size(), after,
-                                         ctypes.byref(t)), "copier_submit")
-            s.ticket = t.value
-            self.last_ticket = t.value
-            return
-        with torch.cuda.stream(s.s):
-            dst.copy_(src, non_blocking=True)
-
-    def wait_copies(self):
-        """[host] Blocks until every frame copy submitted so far has landed in host memory.  The copier thread's SDMA copies are on no stream:
-        torch.cuda.synchronize() does not wait for them (bench.py stops its clock behind this)."""
-        if self.copier is not None and getattr(self, "last_ticket", None) is not None:
-            from ._lib import check, lib
-            check(lib().pn_copier_wait(self.copier, self.last_ticket), "copier_wait")
-
-    # ---- host side of a retired workspace
-    def complete(self, ws):
-        return self.h.model.render_status(synchronize=False, slot=ws)["alive_at_exit"] == 0
-
-    def finish(self, ws):
-        """The captured trips were not enough for this frame: keep going on the workspace's lane until no ray is alive (blocking), then copy
-        the finished frame out again."""
-        h, m = self.h, self.h.model
-        s = self._streams[f"lane{ws // self.depth}"]
-        with torch.cuda.stream(s):
-            with h._amp():
-                kw = self._ws_kw(ws)
-                kw.pop("frame_slot")
-                if "point_pose" in kw:
-                    m.p_def, m.IP_F, m.IP_dF = self.ip[ws]   # the point overlay paints the state this frame was rendered from
-                m.render_continue(ws, self.rays[ws]["rays_o"], self.rays[ws]["rays_d"], self.out[ws], bg_color=None, **kw)
-            if self.host[ws] is not None:
-                self.copy_out(_HipStream(s), ws, same_buffer=True)
-        s.synchronize()
-        self.continued += 1
-        if self.continued == 8:
-            # the launch form baked into the graphs (fused_from / fused_whole / fused_fold, the trip count) came from ONE warm-up frame; a scene or pose
-            # that has moved away from it makes every frame end here, blocking — correct, only slow (round-4 advisor): say so once
-            import warnings
-            warnings.warn("8 frames of this pipeline had rays alive behind their captured trips and were finished by blocking renders: the launch form picked "
-                          "at capture no longer fits the scene / pose — capture_pipelined() again from the current state", RuntimeWarning, stacklevel=2)
-
-    def result(self, ws):
-        o = self.out[ws]
-        H, W, N = self.H, self.W, self.H * self.W
-        dev = {"image": o["image"].view(-1, H, W, 3), "depth": o["depth"].view(-1, H, W), "depth_0": o["depth_0"].view(-1, H, W)}
-        if "point_id" in o:   # draw_points(): on the device only (pick_drawn reads one value)
-            dev.update(point_id=o["point_id"].view(-1, H, W), point_t=o["point_t"].view(-1, H, W), ip_pos=self.ip[ws][0])
-        if self.host[ws] is None:
-            return {"device": dev}
-        hb = self.host[ws][self.host_gen[ws]].numpy()
-        return {"image": hb[:3 * N].reshape(H, W, 3), "depth": hb[3 * N:4 * N].reshape(H, W), "depth_0": hb[4 * N:].reshape(H, W), "device": dev}

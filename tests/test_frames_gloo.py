@@ -193,7 +193,7 @@ def _form_worker(rank, world, port, src, out_dir):
 
 @pytest.mark.parametrize("world,src", [(2, 0), (3, 1)])
 def test_ranks_agree_on_the_owners_launch_form(tmp_path, world, src):
-    """harness._HipBackend's broadcast of (fused_from, fused_whole, fused_fold) with the DEFAULT process group (group=None): every rank ends with
+    """pipeline_hip._HipBackend's broadcast of (fused_from, fused_whole, fused_fold) with the DEFAULT process group (group=None): every rank ends with
     rank src's choice.  Round 5 gated this on `group is not None`, which no real call site satisfies — the ranks kept their own answers."""
     mp.spawn(_form_worker, args=(world, _free_port(), src, str(tmp_path)), nprocs=world, join=True)
     got = [np.load(tmp_path / f"f{r}.npy").tolist() for r in range(world)]

@@ -361,7 +361,7 @@ def eager_frames(small_opt, small_cloud, ckpt):
 def test_captured_step_in_a_wind_equals_eager_steps(small_opt, small_cloud, ckpt, eager_frames):
     frames, disp = eager_frames
     g = _harness(small_opt, small_cloud, ckpt).capture(n_trips=8)
-    assert g._graph_fields and g.sim.field_clock() == 0 and torch.equal(g.sim.dof, g.sim.dof_rest)   # the warm-up steps left neither the clock nor the state advanced
+    assert "fields" in g._captured_graph.stages and g.sim.field_clock() == 0 and torch.equal(g.sim.dof, g.sim.dof_rest)   # the warm-up steps left neither the clock nor the state advanced
     for f in range(4):
         b = g.step_graph()
         g.finish_graph_frame()
@@ -379,7 +379,7 @@ def test_captured_step_in_a_wind_equals_eager_steps(small_opt, small_cloud, ckpt
     assert d > 1e-3
     # a graph captured without the field launches refuses to run once fields are enabled
     plain = SimRenderHarness(dict(small_opt, W=32, H=32), cloud=small_cloud, ckpt=ckpt, device=DEV).capture(n_trips=8)
-    assert not plain._graph_fields
+    assert "fields" not in plain._captured_graph.stages
     plain.step_graph()
     plain.finish_graph_frame()
     plain.sim.enable_fields()
@@ -390,7 +390,7 @@ def test_captured_step_in_a_wind_equals_eager_steps(small_opt, small_cloud, ckpt
 def test_pipelined_frames_in_a_wind_equal_eager_steps(small_opt, small_cloud, ckpt, eager_frames):
     frames, disp = eager_frames
     p = _harness(small_opt, small_cloud, ckpt).capture_pipelined(lanes=2, depth=2, n_trips=8)
-    assert p._pipe_fields and p.sim.field_clock() == 0
+    assert "fields" in p._captured_pipe.stages and p.sim.field_clock() == 0
     got = []
     for f in range(4):
         for idx, res in p.step_pipelined():

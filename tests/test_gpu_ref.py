@@ -731,7 +731,7 @@ def test_full_size_chair_frame_on_the_reference_kernels():
     REPORT["frame_full_size_chair"] = dict(trips=st["trips"], samples=st["samples"], image_max_abs=e_img, weights_sum_max_abs=e_ws, record=a["record"])
     print(REPORT["frame_full_size_chair"])
     assert e_img < 1e-4 and e_ws < 1e-4
-    # ... and by the launch sets bench.py's pipelines run (harness._HipBackend: three lanes = the first trip's network / composite / compaction folded into
+    # ... and by the launch sets bench.py's pipelines run (pipeline_hip._HipBackend: three lanes = the first trip's network / composite / compaction folded into
     # the fused launch on 128 workgroups, march pass 1 in its throughput form; two lanes = the whole frame in the launch on 160 workgroups): the modes that
     # produce `value` against the reference's kernels first-hand, not through the trip-by-trip form
     forms = {"fold_128_three_lanes": dict(fused_from=1, fused_whole=False, fused_fold=True, fused_grid=128, march_throughput=64),

@@ -395,7 +395,7 @@ def test_captured_step_equals_eager_steps(small_opt, small_cloud, ckpt, eager_fr
     frames, disp, _ = _eager(small_opt, small_cloud, ckpt, K_SET + 2, change_at=K_SET)
     assert np.array_equal(disp[K_SET - 1], eager_frames[1][K_SET - 1]) and rel_err(disp[K_SET], eager_frames[1][K_SET]) > 1e-6   # the change changes the run
     g = _harness(small_opt, small_cloud, ckpt).capture(n_trips=8)
-    assert g._graph_self and rel_err(g.sim.dof.cpu().numpy(), _map_dof(g.sim, SQUEEZED)) == 0.0    # the warm-up steps left the state where it was
+    assert "self" in g._captured_graph.stages and rel_err(g.sim.dof.cpu().numpy(), _map_dof(g.sim, SQUEEZED)) == 0.0    # the warm-up steps left the state where it was
     for f in range(K_SET + 2):
         if f == K_SET:
             _change(g.sim)                                                 # followed without a recapture: the state is device memory
@@ -414,7 +414,7 @@ def test_captured_step_equals_eager_steps(small_opt, small_cloud, ckpt, eager_fr
     assert d > 1e-3
     # a graph captured without the stage's launches refuses to run once it is enabled
     plain = _harness(small_opt, small_cloud, ckpt, W=32, enable=False).capture(n_trips=8)
-    assert not plain._graph_self
+    assert "self" not in plain._captured_graph.stages
     plain.step_graph()
     plain.finish_graph_frame()
     plain.sim.enable_self_contact()
@@ -425,7 +425,7 @@ def test_captured_step_equals_eager_steps(small_opt, small_cloud, ckpt, eager_fr
 def test_pipelined_frames_equal_eager_steps(small_opt, small_cloud, ckpt, eager_frames):
     frames, disp = eager_frames
     p = _harness(small_opt, small_cloud, ckpt).capture_pipelined(lanes=2, depth=2, n_trips=8)
-    assert p._pipe_self
+    assert "self" in p._captured_pipe.stages
     got = []
     for f in range(4):
         for idx, res in p.step_pipelined():
