@@ -4,7 +4,8 @@
 tools/time_colliders.py times the HIP launch against (the tests compare the launch with tests/colliders_reference.py's numpy instead).
 
 ``shadow_light`` builds the directional light of the shadowed launch (pn_draw_colliders_shadowed) and ``shadow_rays`` the parallel rays its
-opacity map is rendered along (NeRFRenderer.set_collider_shadows).
+opacity map is rendered along (NeRFRenderer.set_collider_shadows).  The renderer's side — the overlay's state, the shadow pass, the launch — is
+nerf/overlay_colliders.py.
 """
 import math
 

@@ -298,9 +298,9 @@ class SimRenderHarness:
         if ov is None or not self.sim.bodies_enabled:
             return
         live = self.sim.collider_state()
-        if self._collider_snapshot is None or ov[0] is not self._collider_snapshot:
+        if self._collider_snapshot is None or ov.state is not self._collider_snapshot:
             self._collider_snapshot = live.clone()
-            self.model.set_collider_overlay(self._collider_snapshot, ov[1], ov[2])
+            self.model.set_collider_overlay(self._collider_snapshot, ov.style, ov.t_max)
         self._collider_snapshot.copy_(live)
 
     def _order_overlay_behind_setters(self):

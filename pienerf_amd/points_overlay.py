@@ -1,7 +1,8 @@
 """The simulator's integration points and the drag handle drawn into a rendered frame (csrc/pn_points_overlay.hip; include/pienerf_hip.h: pn_draw_points
 has the law).
 
-``point_style`` builds the launch pair's by-value style; ``key_buffer`` allocates the per-frame key buffer, filled once with the empty value.
+``point_style`` builds the launch pair's by-value style; ``key_buffer`` allocates the per-frame key buffer, filled once with the empty value.  The
+renderer's side — the overlay's state, the key buffers per frame workspace, the launch pair — is nerf/overlay_points.py.
 """
 import math
 

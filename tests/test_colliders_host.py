@@ -223,6 +223,7 @@ def test_collider_state_needs_contact_enabled(small_cloud, small_opt):
 
 def test_overlay_arguments_are_checked_and_other_renders_refuse():
     import torch
+    from pienerf_amd.nerf.overlay_colliders import ColliderOverlay
     from pienerf_amd.nerf.renderer import NeRFRenderer
     r = NeRFRenderer(bound=1, cuda_ray=True)
     assert r.collider_overlay_key() is None
@@ -230,7 +231,7 @@ def test_overlay_arguments_are_checked_and_other_renders_refuse():
         r.set_collider_overlay(torch.zeros(92, dtype=torch.float64))
     with pytest.raises(RuntimeError, match="GPU"):
         r.set_collider_overlay(torch.zeros(93, dtype=torch.float64))   # host memory: the launch reads the state on the device
-    r._overlay = (torch.zeros(93, dtype=torch.float64), None, 8.0)     # as if set: the refusals need no device
+    r._overlay = ColliderOverlay(torch.zeros(93, dtype=torch.float64), None, 8.0)     # as if set: the refusals need no device
     rays = torch.zeros(4, 3)
     for call in (lambda: r.rund_cuda(rays, rays, perturb=True), lambda: r.run_cuda(rays, rays), lambda: r.run(rays, rays),
                  lambda: r.rund_cuda_ops(rays, rays)):

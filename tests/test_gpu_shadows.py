@@ -204,7 +204,7 @@ def test_render_with_shadows(chair):
     # the map buffers: the light's rays through the existing render
     assert _same(m.shadow_ws, direct["weights_sum"]) and _same(m.shadow_depth_0, direct["depth_0"])
     assert int((m.shadow_ws > 0.5).sum()) > 20 and int((m.shadow_ws == 0).sum()) > 20
-    assert bytes(m._shadows["light"]) == bytes(shadow_light(direction=LIGHT, resolution=RES, bound=h.opt["bound"], min_near=h.opt["min_near"]))
+    assert bytes(m._shadows.light) == bytes(shadow_light(direction=LIGHT, resolution=RES, bound=h.opt["bound"], min_near=h.opt["min_near"]))
     # the frame's statistics stay the main frame's; the shadow slot has its own
     st = m.render_status(slot=m.SHADOW_SLOT)
     assert st["err"] == 0 and st["alive_at_exit"] == 0 and 0 < st["samples"] != main_stats["samples"]
@@ -215,7 +215,7 @@ def test_render_with_shadows(chair):
     got, base = _np(shad["image"]), _np(drawn["image"])
     assert np.array_equal(_bits(got[sh == 0]), _bits(base[sh == 0]))
     assert (got[sh > 0] <= base[sh > 0]).all() and (got[sh > 0] < base[sh > 0]).any()
-    lt = _light_dict(m._shadows["light"])
+    lt = _light_dict(m._shadows.light)
     ws, wd = _np(m.shadow_ws), _np(m.shadow_depth_0)
     args = (h.sim._colliders, GC._style_rgb(h.style), h.style.checker, h.style.checker_dim, h.style.ambient, _np(r["rays_o"]), _np(r["rays_d"]),
             h.opt["min_near"], 8.0 * h.opt["bound"], 1.0, over0["weights_sum"], over0["depth_0"], over0["image"])
@@ -259,8 +259,8 @@ def test_one_trip_render_finished_by_render_continue_equals_the_blocking_render(
     with torch.no_grad():
         m.render_continue(0, r["rays_o"], r["rays_d"], part, bg_color=None, **dict(h.render_kwargs(), fused_from=-1))
         sh = m._shadows
-        m.rund_cuda(sh["rays_o"], sh["rays_d"], bg_color=0, **dict(h.render_kwargs(), async_trips=1, fused_from=-1, frame_slot=m.SHADOW_SLOT,
-                                                                    out_buffers=m._shadow_out(), ray_tile_w=0, _shadow_pass=True))
+        m.rund_cuda(sh.rays_o, sh.rays_d, bg_color=0, **dict(h.render_kwargs(), async_trips=1, fused_from=-1, frame_slot=m.SHADOW_SLOT,
+                                                                    out_buffers=sh.out(), ray_tile_w=0, _shadow_pass=True))
         assert m.render_status(slot=0)["alive_at_exit"] == 0 and m.render_status(slot=m.SHADOW_SLOT)["alive_at_exit"] > 0
         done = m.render_continue(0, r["rays_o"], r["rays_d"], part, bg_color=None, **dict(h.render_kwargs(), fused_from=-1))
     torch.cuda.synchronize()

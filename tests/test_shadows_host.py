@@ -248,16 +248,17 @@ def test_light_mirror_follows_the_header():
 def test_shadows_need_an_overlay_and_are_cleared_with_it():
     import torch
     from pienerf_amd.colliders import collider_style, shadow_light
+    from pienerf_amd.nerf.overlay_colliders import ColliderOverlay
     from pienerf_amd.nerf.renderer import NeRFRenderer
     r = NeRFRenderer(bound=1, cuda_ray=True)
     with pytest.raises(RuntimeError, match="set_collider_overlay"):
         r.set_collider_shadows(shadow_light())
-    r._overlay = (torch.zeros(93, dtype=torch.float64), collider_style(), 8.0)     # as if set: host memory is enough for the bookkeeping
+    r._overlay = ColliderOverlay(torch.zeros(93, dtype=torch.float64), collider_style(), 8.0)     # as if set: host memory is enough for the bookkeeping
     key0 = r.collider_overlay_key()
     with pytest.raises(ValueError, match="ShadowLight"):
         r.set_collider_shadows("sun")
     r.set_collider_shadows(shadow_light(resolution=8))
-    assert r.shadow_ws.shape == r.shadow_depth_0.shape == (64,) and r._shadows["rays_o"].shape == (64, 3)
+    assert r.shadow_ws.shape == r.shadow_depth_0.shape == (64,) and r._shadows.rays_o.shape == (64, 3)
     key1 = r.collider_overlay_key()
     assert key1[:len(key0)] == key0 and len(key1) == len(key0) + 3      # the light's bytes and the two maps' addresses, only with shadows
     assert key1[-2:] == (r.shadow_ws.data_ptr(), r.shadow_depth_0.data_ptr())
