@@ -843,6 +843,46 @@ int pn_sim_self_rhs(int n_k, int n_IP, void* state, void* work, double dt, doubl
                     const int* topo, const double* rho, const double* Nx, const int* kernel_bg, const int* kernel_cnt, const int* buffer,
                     const double* Nx_csr, const double* rhs_in, double* rhs_out, double* accel_out, void* stream);
 
+/* Simulator diagnostics (csrc/pn_diagnostics.hip; Simulator.diagnostics): what a state (dof, dof_vel) holds, as one row of
+ * PN_DIAG_DOUBLES doubles.  A readout, not a stage: it writes `work`, `row_out` and `per_point` only, so a run with it and a run without it are the same
+ * bits.  THE LAW, everything fp64.  Per integration point p with its 8 kernels, m = rho[p] dx^3 and j = rho[p] dx^5 / 12:
+ *   x, v         position and velocity by pn_ip_state (csrc/pn_sim_rhs.h): what contact, the force fields and self-contact see;
+ *   F, G         sum over the kernels of dof (x) dNx and dof_vel (x) dNx, a kernel's share as the substep's ip_F_partial forms it, the shares added over the
+ *                point's eight lanes ^1, ^2, ^4;
+ *   H            sum of dof (x) ddNx, the 27 components pn_sim_update_F calls dF;
+ *   sig          the converged cold-start Jacobi svd3 of F (csrc/pn_sim_svd.h): |sig| descending, sig[2] carries the sign of det F.  Never the
+ *                McAdams approximation, whatever decomposition the solver runs: this is a measurement;
+ *   sp           volume_invariant_project(sig) (simulator/func_utils.py:21-40);  det = det F, from F directly.
+ * The energies are the ones the solver's own matrix stands for (build_IP_global, simulator/cuda_utils.py:48-55: c0 = rho dx^3 / dt^2 on Nx, c1 =
+ * dx^3 (rho dx^2 / 12 / dt^2 + mu + lam) on dNx, c2 = dx^5 (mu + lam) / 12 on ddNx):
+ *   kinetic      ke = 1/2 m |v|^2 + 1/2 j |G|_F^2
+ *   elastic      ee = dx^3 (mu/2 sum (sig_i - 1)^2 + lam/2 sum (sig_i - sp_i)^2) + (dx^5 / 12) (mu + lam)/2 |H|^2      (mu = mu[p], lam = lam[p];
+ *                sum (sig_i - 1)^2 = |F - R|^2 and sum (sig_i - sp_i)^2 = |F - V|^2 of calc_elastic, so neither U nor V enters)
+ *   gravity      ge = -m g.x
+ *   momentum     P = m v;   L = m x cross v + j sum_c F[:,c] cross G[:,c]   (about the origin)
+ *   strain       sqrt(sum (sig_i - 1)^2);   speed |v|.
+ * A point is NON-FINITE when any of x, v, F, G, H is not finite, or one of its kernel ids is outside [0, n_k) (never with the tables solver.py builds):
+ * it is counted and excluded from every sum and every extremum.  The row, PN_DIAG_DOUBLES doubles (Python: diagnostics.DIAG_FIELDS):
+ *   [0] mass   [1..3] com = sum m x / mass   [4..6] P   [7..9] L   [10] kinetic   [11] gravity   [12] elastic
+ *   [13,14] sig_min (over sig[2])   [15,16] sig_max (over sig[0])   [17,18] det_min   [19,20] strain_max   [21,22] speed_max: (value, point index as a double);
+ *   on equal values the lowest index;  [23] nonfinite   [24] inverted (points with det <= 0).
+ * With no finite point the sums are 0 and the extrema NaN with index -1.  The pin penalty's energy is NOT part of `elastic`: the pins act on cloud
+ * points, not integration points, and kinematic pins move their targets.
+ * per_point (may be NULL): [n_IP, 8] = (m, ke, ee, det, sig0, sig1, sig2, strain); NaN behind m for a non-finite point.
+ * work >= pn_sim_diagnostics_work_doubles(n_IP) doubles: one partial record per 32 points.  g3_host: the gravity vector, read in the call.
+ * TWO launches on `stream` (eight lanes per point and one record per workgroup, then one workgroup that folds the records in ascending order), no
+ * atomics, fixed summation trees: the same bits from every run on the same inputs.  PN_ERR_ARG, before anything is enqueued, for a NULL pointer
+ * (per_point excepted), n_k or n_IP <= 0, n_IP > 2^27, dx not finite or not > 0.  No allocation, no host synchronisation, capturable. */
+#define PN_DIAG_DOUBLES 25
+int pn_sim_diagnostics(int n_k, int n_IP, double dx, const double* g3_host, const double* dof, const double* dof_vel, const int* topo, const double* rho,
+                       const double* mu, const double* lam, const double* Nx, const double* dNx, const double* ddNx, double* work, double* row_out,
+                       double* per_point, void* stream);
+/* PN_DIAG_DOUBLES, for the Python side to check its DIAG_FIELDS against (the row of pn_sim_diagnostics; energies of simulator/cuda_utils.py:48-55). */
+int pn_sim_diagnostics_doubles(void);
+/* Doubles of pn_sim_diagnostics's `work` for n_IP points (the partial records of its first launch; simulator/cuda_utils.py:48-55 has no counterpart:
+ * the reference never sums its energies). */
+uint64_t pn_sim_diagnostics_work_doubles(int n_IP);
+
 /* The colliders drawn into a rendered frame (csrc/pn_colliders.hip; NeRFRenderer.set_collider_overlay): one launch behind the frame
  * driver, a thread per ray, composites the analytic surfaces of a pn_contact_state into `image` with a depth test against the object.  `contact_state`
  * is DEVICE memory with the pn_contact_state layout (the simulator's own buffer or a 744-byte copy), read at execution time: a captured launch follows

@@ -162,6 +162,9 @@ SIGNATURES = {
     "pn_sim_self_launches": (i32, []),
     "pn_sim_self_set_params": (i32, [P, i32, P, P]),
     "pn_sim_self_rhs": (i32, [i32, i32, P, P, f64, f64, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "pn_sim_diagnostics": (i32, [i32, i32, f64, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "pn_sim_diagnostics_doubles": (i32, []),
+    "pn_sim_diagnostics_work_doubles": (u64, [i32]),
     "pn_draw_colliders": (i32, [P, C.POINTER(ColliderStyle), P, P, u32, f32, f32, f32, P, P, P, P, P, P]),
     "pn_draw_colliders_shadowed": (i32, [P, C.POINTER(ColliderStyle), P, P, u32, f32, f32, f32, P, P, P, P, P, ShadowLight, P, P, P, P]),
     "pn_points_keys_bytes": (u64, [i32, i32]),

@@ -56,6 +56,9 @@ UNITS = {
     "pn_bodies.hip": ["-ffp-contract=fast"],
     # the one decision self-contact takes in floating point (a pair's eligibility at rest) switches contraction off for itself
     "pn_selfcontact.hip": ["-ffp-contract=fast"],
+    # the diagnostics readout: pn_sim_rhs.h's point state and pn_sim_svd.h's ip_F_partial / svd3, contracted as in the units it shares them with;
+    # fp64 sums in fixed trees, compared with tests/diagnostics_reference.py by a derived tolerance
+    "pn_diagnostics.hip": ["-ffp-contract=fast"],
     # the colliders drawn into a frame: per-ray fp32 with decisions in it (hit / miss, checker parity, in front of / behind the object), one rounding per
     # operation in source order, which tests/colliders_reference.py restates in numpy; a ray without a hit gets the frame epilogue's two roundings
     "pn_colliders.hip": ["-ffp-contract=off"],

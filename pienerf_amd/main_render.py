@@ -15,6 +15,7 @@ deformed point cloud and the per-frame IP state the reference's ``main_render.py
            [--point_alpha 1] [--point_hidden_alpha 0] [--no_drag_marker]]
            [--save_mesh [--mesh_resolution 128] [--mesh_threshold 10] [--mesh_con 0] [--mesh_normals] [--mesh_color]]
            [--video [PATH] [--fps 30] [--video_quality 90] [--video_subsampling 420|444] [--no_png]]
+           [--diagnostics [CSV]] [--until_rest KE]
 
 Without --ply / --ckpt the synthetic chair of pienerf_amd.scene is used (there are no assets on the GPU box).
 --save_mesh writes the deforming surface: the model's density level set, meshed once at rest, bound to the simulator (Simulator.bind_points) and warped
@@ -49,6 +50,11 @@ point and the cursor get the reference's red and blue discs and the line between
 baseline JPEG on the device, from the tensor the step returns, and only the finished bitstream crosses to the host; frame f of the video is the JPEG of
 img_f.png's pixels.  --no_png leaves the PNGs out, and then the fp32 image is not copied to the host at all.  It composes with every other flag (the
 overlays are part of the image).  python -m pienerf_amd.video OUT/video.avi --extract DIR writes the frames out as .jpg files.
+--diagnostics measures every frame's state on the device (Simulator.record_diagnostics; default CSV: OUT/diagnostics.csv): mass, centre of
+mass, momenta, kinetic / gravitational / elastic energy, the extrema of the singular values, det F, strain and speed with their integration points, and the
+counts of non-finite and inverted points.  Row f is recorded immediately before frame f's step — the state img_f.png shows — with no synchronisation in
+the loop; one read after it writes the CSV and reports the first frame with a non-finite or inverted point.  --until_rest KE stops the run after the
+first frame whose kinetic energy is below KE (one 8-byte host read per frame) and implies --diagnostics.  They compose with every other flag.
 Without --ckpt a --save_mesh run renders and meshes the SHAPED synthetic checkpoint (its density field has the solid's shape; the plain one's does not).
 Reference: main_gui.py:20-66 (model + simulator construction), nerf/gui.py:556-645 (test_step: IP info -> substep -> render),
 main_render.py:47-104 (frame loop, save_image), simulator/solver.py:109-113 (OutputToPly).
@@ -284,6 +290,34 @@ def check_video_args(args):
         raise SystemExit("--fps is positive")
 
 
+def check_diagnostics_args(args):
+    """What --until_rest refuses, before anything is built."""
+    ke = getattr(args, "until_rest", None)
+    if ke is not None and not (np.isfinite(ke) and ke > 0):
+        raise SystemExit(f"--until_rest: KE is a positive finite kinetic energy, got {ke!r}")
+
+
+def diagnostics_path(args):
+    """Where --diagnostics writes: its argument, or OUT/diagnostics.csv; None without --diagnostics and without --until_rest."""
+    if getattr(args, "diagnostics", None) is None and getattr(args, "until_rest", None) is None:
+        return None
+    return getattr(args, "diagnostics", None) or os.path.join(args.out, "diagnostics.csv")
+
+
+def report_diagnostics(rows):
+    """The line a --diagnostics run prints: the first frame with a non-finite or inverted point (or that there is none), the last frame's energies."""
+    from .simulator.diagnostics import DIAG_FIELDS
+    col = {n: i for i, n in enumerate(DIAG_FIELDS)}
+    bad = [f for f, r in enumerate(rows) if r[col["nonfinite"]] > 0 or r[col["inverted"]] > 0]
+    if bad:
+        r = rows[bad[0]]
+        first = f"first frame with a non-finite or inverted point: {bad[0]} ({int(r[col['nonfinite']])} non-finite, {int(r[col['inverted']])} inverted)"
+    else:
+        first = "no frame with a non-finite or inverted point"
+    last = rows[-1]
+    return f"diagnostics: {len(rows)} frames, {first}; last frame: kinetic {last[col['kinetic']]:.6g}, elastic {last[col['elastic']]:.6g}"
+
+
 def video_path(args):
     """Where --video writes: its argument, or OUT/video.avi; None without --video."""
     if args.video is None:
@@ -320,6 +354,7 @@ def open_video(args, device):
 
 def run(args):
     check_video_args(args)
+    check_diagnostics_args(args)
     if args.pin_centre is not None and args.pin_twist is None:
         raise SystemExit("--pin_centre is the centre of --pin_twist")
     check_overlay_args(args)
@@ -354,8 +389,14 @@ def run(args):
         if not args.quiet:
             print(f"mesh: {binding.V} vertices, {len(triangles)} triangles; {binding.n_fallback} vertices bound through their nearest integration point")
     video = open_video(args, h.device)
-    written, t0 = [], time.time()
+    diag_csv, diag_log = diagnostics_path(args), None
+    if diag_csv is not None:
+        from .simulator.diagnostics import DIAG_FIELDS, DiagnosticsLog
+        diag_log = DiagnosticsLog(max(args.frames, 1), h.device)
+        ke_col = DIAG_FIELDS.index("kinetic")
+    written, t0, done = [], time.time(), 0
     for f in range(args.frames):
+        done = f + 1
         if args.drag is not None:
             x0, y0, x1, y1 = args.drag
             t = f / max(args.frames - 1, 1)
@@ -372,6 +413,8 @@ def run(args):
             pos, nrm = w if args.mesh_normals else (w, None)
             scene.write_mesh_ply(os.path.join(args.out, f"mesh_{f}.ply"), pos.cpu().numpy(), triangles,
                                  normals=nrm.cpu().numpy() if nrm is not None else None, colors=colors)
+        if diag_log is not None:   # BEFORE the step, like the mesh: row f is the state img_f.png shows; enqueued between two substeps, no synchronisation
+            h.sim.record_diagnostics(diag_log)
         out = h.step(pose=pose, collect_stats=True)
         if video is not None:   # from the device tensor, before the host copy: the bitstream crosses, not the floats
             video.add(out["image"])
@@ -387,11 +430,21 @@ def run(args):
         if args.save_ply:
             h.synchronize()
             h.sim.OutputToPly(os.path.join(args.out, f"points_{f}.ply"))
+        if args.until_rest is not None:   # the one 8-byte read of the frame: row f's kinetic energy
+            if h.sim._host_read(lambda: float(diag_log.rows[f, ke_col].item())) < args.until_rest:
+                if not args.quiet:
+                    print(f"until_rest: the kinetic energy of frame {f} is below {args.until_rest:g}: stopping")
+                break
     h.synchronize()
+    if diag_log is not None:
+        rows = diag_log.to_numpy()   # the one read
+        diag_log.write_csv(diag_csv, rows)
+        if not args.quiet and len(rows):
+            print(report_diagnostics(rows) + f" -> {os.path.abspath(diag_csv)}")
     if video is not None:
         video.close()
         if not args.quiet:
-            print(f"video: {args.frames} frames, {video.bytes} bytes of JPEG -> {os.path.abspath(video.path)}")
+            print(f"video: {done} frames, {video.bytes} bytes of JPEG -> {os.path.abspath(video.path)}")
     if h.sim.contact_enabled and not args.quiet:
         print(f"contact: {h.sim.contact_count()} of {h.sim.n_IP} integration points in contact in the last substep")
     if h.sim.bodies_enabled and not args.quiet:
@@ -402,7 +455,7 @@ def run(args):
         print(f"self-contact: {h.sim.self_contact_count()} of {h.sim.n_IP} integration points in contact with the body itself in the last substep, "
               f"{h.sim.self_contact_overflows()} substeps over the bucket cap")
     if not args.quiet:
-        print(f"{args.frames} frames -> {os.path.abspath(args.out)} in {time.time() - t0:.2f} s; last frame: {h.model.last_stats}")
+        print(f"{done} frames -> {os.path.abspath(args.out)} in {time.time() - t0:.2f} s; last frame: {h.model.last_stats}")
     return written
 
 
@@ -498,6 +551,11 @@ def parser():
     ap.add_argument("--video_quality", type=int, default=90, help="JPEG quality of the video's frames, 1 .. 100 (libjpeg's scale)")
     ap.add_argument("--video_subsampling", choices=("420", "444"), default="420", help="chroma at half resolution on both axes, or at full resolution")
     ap.add_argument("--no_png", action="store_true", help="with --video: write no img_{f}.png, and copy no fp32 image to the host")
+    ap.add_argument("--diagnostics", nargs="?", const="", default=None, metavar="CSV",
+                    help="measure every frame's state on the device (energies, momenta, strain extrema; DESIGN.md 4.18) and write one row per frame; "
+                    "default CSV: OUT/diagnostics.csv")
+    ap.add_argument("--until_rest", type=float, default=None, metavar="KE",
+                    help="stop after the first frame whose kinetic energy is below KE > 0; costs one 8-byte host read per frame; implies --diagnostics")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--quiet", action="store_true")
     return ap

@@ -17,11 +17,12 @@ import torch
 
 from .. import scene
 from .._lib import check, lib, ptr, stream_ptr
-from . import bodies, contact, drag, fields, gmls, pins, selfcontact
+from . import bodies, contact, diagnostics, drag, fields, gmls, pins, selfcontact
 from ._stage import StageHost, _null_ctx, _vec3, npfloat, torchfloat  # noqa: F401
 # every module-level name this file had before the stages moved into files of their own is still importable from here
 from .bodies import *  # noqa: F401,F403
 from .contact import *  # noqa: F401,F403
+from .diagnostics import *  # noqa: F401,F403
 from .drag import *  # noqa: F401,F403
 from .drag import _check_scale  # noqa: F401
 from .fields import *  # noqa: F401,F403
@@ -32,7 +33,7 @@ from .selfcontact import *  # noqa: F401,F403
 CELL_CHUNK_IPS = 32   # points per chunk of the substep's cell form = pn_sim_cells_chunk_ips() (csrc/pn_sim_cells.h: PN_CELL_IPS), checked in _prepare_cells
 
 
-class Simulator(StageHost, DragMixin, PinsMixin, ContactMixin, BodiesMixin, FieldsMixin, SelfContactMixin):  # noqa: F405
+class Simulator(StageHost, DragMixin, PinsMixin, ContactMixin, BodiesMixin, FieldsMixin, SelfContactMixin, DiagnosticsMixin):  # noqa: F405
     # The substep's stages, in the order stepforward() enqueues them.  Drag stands in front: it writes dof_f, not the right-hand side.  The others are
     # links of one chain, each writing (what the link before it wrote) + its own term into a buffer of its own, and the substep takes the last link in
     # its rhs_gravity slot: rhs_gravity -> pins -> contact -> fields -> self.  Pins lead because their term depends on time alone; contact, fields and
@@ -74,6 +75,7 @@ class Simulator(StageHost, DragMixin, PinsMixin, ContactMixin, BodiesMixin, Fiel
         self.res = (bbox // dx).to(dtype=torch.int32).to(self.device)
         self.base = base.to(dtype=torchfloat).to(self.device)
         self.gravity = gravity.to(dtype=torchfloat).to(self.device)
+        self.gravity_host = np.ascontiguousarray(gravity.detach().cpu().numpy(), dtype=npfloat).reshape(3)   # for the launches that take it by value (diagnostics.py)
         self.dof = None
         self._work = None
         self._prepared = False   # pn_sim_prepare has run on _work (with the first substep: the CSR lists it reads are built by precompute)
