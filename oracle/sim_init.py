@@ -147,16 +147,21 @@ def build_IP_global(dx, dt, topo, mu, lam, rho, Nx, dNx, ddNx, dim):
             for q in range(3):
                 dd = ddNx[v, :, p, q, :].reshape(80)
                 blk += c2 * np.outer(dd, dd)
-        mat[np.ix_(rows[v], rows[v])] += blk
+        mat[np.ix_(rows[v], rows[v])] += blk   # rows[v]: an integration point's 8 kernels are the 8 distinct corners of its own kernel-grid cell, all
+        #                                          inside the kernel mask, so no index repeats here (a POINT's row can repeat one: build_pin_global)
     return mat
 
 
 def build_pin_global(stiff, vidx, topo, Nx, mat):
-    """build_pin_global (simulator/cuda_utils.py:58-81)."""
+    """build_pin_global (simulator/cuda_utils.py:58-81).
+
+    A point that is no integration point's centre can name one kernel several times: kernel_idx is 0 outside the kernel mask (solver.py:204-232), so
+    its pts_kernel row may repeat kernel 0.  The reference adds all 64 (i, j) pairs atomically, so repeated rows ACCUMULATE: np.add.at, not
+    ``mat[np.ix_(rows, rows)] +=``, which keeps one of the repeated contributions and drops the rest."""
     for vv in vidx:
-        rows = (np.asarray(topo)[vv][:, None] * 10 + np.arange(10)[None, :]).reshape(80)
+        rows = (np.asarray(topo)[vv].astype(np.int64)[:, None] * 10 + np.arange(10)[None, :]).reshape(80)
         nv = Nx[vv].reshape(80)
-        mat[np.ix_(rows, rows)] += stiff * np.outer(nv, nv)
+        np.add.at(mat, (rows[:, None], rows[None, :]), stiff * np.outer(nv, nv))
     return mat
 
 
@@ -184,7 +189,8 @@ class OracleSimulator:
         self.is_pin = torch.from_numpy(np.asarray(pin).astype(bool))
         self.initialize()
 
-    def initialize(self):  # solver.py:139-331
+    def topology(self):
+        """The grid bookkeeping of initialize() alone (solver.py:139-256): integration points, kernels, IP_kernel and pts_kernel."""
         res, kres = self.res, self.kres
         self.grid_idx = ((self.pos - self.base) // self.dx).to(torch.int32).long()
         r0, r1, r2 = int(res[0]), int(res[1]), int(res[2])
@@ -222,6 +228,10 @@ class OracleSimulator:
         self.kernel_grid = kernel_pos[self.kernel_mask, :]
         self.kernel_pos = self.kernel_grid * self.kdx + self.base
         self.n_k, self.n_IP = n_k, n_IP
+
+    def initialize(self):  # solver.py:139-331
+        self.topology()
+        n_k, n_IP = self.n_k, self.n_IP
 
         kdx = float(self.kdx)
         kp = self.kernel_pos.numpy()

@@ -145,6 +145,9 @@ class Simulator(StageHost, DragMixin, PinsMixin, ContactMixin, BodiesMixin, Fiel
         for x, y, z in corners:
             self.kernel_mask[IP2K[:, 0] + x, IP2K[:, 1] + y, IP2K[:, 2] + z] |= True
         n_k = int(self.kernel_mask.sum())
+        # 0, not -1, outside the mask — as the reference has it (solver.py:204-232).  The mask comes from the integration points' cell centres, so a POINT
+        # near the rim of its cell can lie in a kernel-grid cell with corners outside it: its pts_kernel row then names kernel 0 once or several times.
+        # Reference behaviour, kept; whatever sums over such a row (add_pin_penalty, update_pos, the pin term) adds repeated entries up
         self.kernel_idx = torch.zeros((kres, kres, kres), dtype=torch.int32, device=dev)
         self.kernel_idx[self.kernel_mask] = torch.arange(0, n_k, 1, dtype=torch.int32, device=dev)
         pts2K = ((self.pos - self.base) // self.kdx).to(dtype=torch.int32).long()

@@ -169,3 +169,58 @@ def test_elastic_rhs_vanishes_for_rigid_motion(oracle_sim):
     b0 = oracle.collect_rhs_IP(s.dx, s.IP_kernel.numpy(), s.IP_mu, s.IP_lam, s.IP_dNx, RF0, VF0, s.n_k * 10)
     bQ = oracle.collect_rhs_IP(s.dx, s.IP_kernel.numpy(), s.IP_mu, s.IP_lam, s.IP_dNx, RF, VF, s.n_k * 10)
     assert np.abs(bQ - b0 @ Q.T).max() < 1e-9 * np.abs(b0).max()
+
+
+# ------------------------------------------------------------------------------------------------ the pin penalty with repeated kernels
+def _literal_pin_global(stiff, vidx, topo, Nx, dim):
+    """build_pin_global (simulator/cuda_utils.py:58-81) thread by thread: for every pinned point the 8 x 8 (i, j) pairs, for every pair the 10 x 10
+    (x, y) scalar additions `mat[kid_i 10 + x, kid_j 10 + y] += stiff N_i[x] N_j[y]` — what wp.atomic_add does, repeated indices included."""
+    mat = [[0.0] * dim for _ in range(dim)]
+    for vv in vidx:
+        t, N = [int(k) for k in topo[vv]], Nx[vv].tolist()
+        for i in range(8):
+            for j in range(8):
+                for x in range(10):
+                    row, a = mat[t[i] * 10 + x], stiff * N[i][x]
+                    for y in range(10):
+                        row[t[j] * 10 + y] += a * N[j][y]
+    return np.array(mat)
+
+
+def test_pin_penalty_accumulates_repeated_kernels(oracle_sim):
+    """A point that is no integration point's centre may name kernel 0 several times (kernel_idx is 0 outside the kernel mask, as in the reference), and
+    the reference's kernel then ADDS the repeated (i, j) pairs.  oracle.sim_init.build_pin_global and gmls.add_pin_penalty against the literal loops, on
+    the beam of tests/sim_clouds.py, half of whose 128 pinned points repeat a kernel; round-off, 1e-14 relative (sums of at most 128 x 64 products of
+    one magnitude in different orders).  The form this oracle had before, ``mat[np.ix_(rows, rows)] += ...``, keeps one of the repeated contributions:
+    it is restated here and must MISS the literal loops on this cloud, or the cloud tests nothing.  Neither chair cloud has a point with a repeated
+    kernel, which is what keeps every golden under tests/golden/ (all computed on the chair with the earlier form) valid."""
+    import sim_clouds
+    from oracle.sim_init import OracleSimulator, build_pin_global
+    from pienerf_amd.simulator import gmls
+    ref = make_oracle_sim(sim_clouds.make("beam"), sim_clouds.opt())
+    topo, Nx = ref.pts_kernel.numpy(), ref.pts_Nx
+    vid = np.nonzero(ref.is_pin.numpy())[0]
+    rep = sim_clouds.repeated_rows(topo)
+    assert len(vid) == 128 and int(rep[vid].sum()) == 64
+    dim = ref.n_k * 10
+    want = _literal_pin_global(ref.stiff, vid, topo, Nx, dim)
+    got = build_pin_global(ref.stiff, vid, topo, Nx, np.zeros((dim, dim)))
+    sim = gmls.add_pin_penalty(torch.zeros((dim, dim), dtype=torch.float64), ref.stiff, torch.from_numpy(vid), ref.pts_kernel, torch.from_numpy(Nx)).numpy()
+    dropped = np.zeros((dim, dim))
+    for vv in vid:
+        rows = (topo[vv].astype(np.int64)[:, None] * 10 + np.arange(10)[None, :]).reshape(80)
+        dropped[np.ix_(rows, rows)] += ref.stiff * np.outer(Nx[vv].reshape(80), Nx[vv].reshape(80))
+    e_or, e_sim, e_drop = rel_err(got, want), rel_err(sim, want), rel_err(dropped, want)
+    print(f"pin penalty vs the literal loops: oracle {e_or:.2e}, gmls.add_pin_penalty {e_sim:.2e}, the form that drops repeated rows {e_drop:.2e}")
+    assert e_or < 1e-14 and e_sim < 1e-14
+    assert e_drop > 1e-3
+    # the chair clouds, small and full size: no point repeats a kernel
+    assert not sim_clouds.repeated_rows(oracle_sim.pts_kernel.numpy()).any() and len(oracle_sim.pos) == 1208
+    from pienerf_amd import scene
+    o = scene.default_opt()
+    c = scene.make_chair_points(hgs=o["hash_grid_size"])
+    full = OracleSimulator(dt=o["sim_dt"], iters=o["sim_iters"], bbox=torch.tensor([2.0 * o["bound"]] * 3), dx=o["sim_dx"], stiff=o["sim_stiff"],
+                           base=torch.tensor([-o["bound"]] * 3))
+    full.pos = torch.from_numpy(np.asarray(c["pos"], np.float64))
+    full.topology()
+    assert len(full.pos) == 10296 and full.n_IP == 3576 and not sim_clouds.repeated_rows(full.pts_kernel.numpy()).any()
