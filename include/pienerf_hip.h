@@ -534,6 +534,36 @@ int pn_sim_stepforward_cells(int n_k, int n_chunks, int iters, double dt, double
                              const double* lam_cell, const int* kp_bg, const int* kp_pos, const double* Ainv, const double* Mmat, const double* dof_rest,
                              const double* rhs_rest, const double* rhs_gravity, const double* dof_f, double* dof, double* dof_vel, double* work,
                              int mcadams_sweeps, void* stream);
+/* The global step without a dense matrix (csrc/pn_sim_pcg.h).  The system block of simulator/solver.py:505-511,600 is kept in block-sparse rows over the
+ * kernels: rowptr [n_k + 1], col [nnzb] int32 ascending inside a row, blocks [nnzb][10][10] fp64 row-major (simulator/gmls.py: bsr_pattern,
+ * assemble_IP_bsr).  Y [10 n_k,3] = A X, the product simulator/solver.py:505-511,600 takes with the dense matrix; X != Y.  `blocks` and every vector the
+ * three entries below gather from (X here; X, A and work of pn_sim_pcg_solve; A, M, dof, dof_vel, dof_rest and pcg_work of pn_sim_stepforward_cells_pcg) are
+ * read 16 bytes at a time and must be 16-byte aligned: PN_ERR_ARG otherwise. */
+int pn_sim_bsr_matvec3(int n_k, const int* rowptr, const int* col, const double* blocks, const double* X, double* Y, void* stream);
+/* Solves A X = B (simulator/solver.py:505-511,600: `global_matrix @ rhs` without the inverse) for the three columns of B [10 n_k,3] together by conjugate
+ * gradients preconditioned with Dinv [n_k][10][10], the inverted diagonal blocks (zeros for inactive kernels).  active [n_k] int32: rows and columns of
+ * kernels with active == 0 are left out, their rows of X end as 0.  X holds the initial guess on entry and the solution on exit.  Per column: r = b - A x0;
+ * |b| = 0 gives x = 0 in 0 iterations; a column stops when |r|_2 <= tol |b|_2 on the recurrence residual (tested before the first iteration too: a
+ * converged x0 comes back bit for bit), and is then frozen — its x, r, p are not written again, so its bits do not depend on the other columns; p.Ap <= 0
+ * or not finite freezes it as unconverged; after max_iters (>= 1) the current x stands and it counts as unconverged.  Plain launches only, 2 max_iters + 2
+ * of them, which return at once when every column is frozen; every dot product is a sum of per-workgroup partials added in a fixed order (no
+ * floating-point atomics): the same history gives the same bits.  work >= pn_sim_pcg_work_doubles(n_k) doubles, no initialisation needed: no value that a launch
+ * of this solve has not written enters its arithmetic (an inactive kernel's and a frozen column's entries of p are never read into it), so the result does
+ * not depend on what `work` held (tests/test_gpu_pcg.py fills it with NaN).
+ * stats (int32, device, zeroed by the caller once): [0] solves and [1] unconverged columns, running totals; [2 + 6 s + c] iterations and [5 + 6 s + c]
+ * flag (1 converged, 0 stopped by max_iters, 2 p.Ap breakdown) of column c in slot s — pn_sim_pcg_solve writes slot 0 (8 ints). */
+uint64_t pn_sim_pcg_work_doubles(int n_k);
+int pn_sim_pcg_solve(int n_k, const int* rowptr, const int* col, const double* A, const double* Dinv, const int* active, const double* B, double* X,
+                     double tol, int max_iters, double* work, int* stats, void* stream);
+/* pn_sim_stepforward_cells with the dense product of simulator/solver.py:505-511,600 replaced by that solve: A and M (the mass block, same pattern) instead
+ * of Ainv and Mmat.  Momentum goes through the BSR product with M; every local/global iteration is k_cells_elastic_gather, a solve warm-started from
+ * dof - dof_rest, dof = dof_rest + x, the last one also dof_vel.  `work` as pn_sim_stepforward_cells has it, pcg_work >= pn_sim_pcg_work_doubles(n_k);
+ * stats >= 2 + 6 iters ints: slot s = local/global iteration s of this (the last) substep. */
+int pn_sim_stepforward_cells_pcg(int n_k, int n_chunks, int iters, double dt, double dx, const int* chunk_tab, const double* dNx_cell, const double* mu_cell,
+                                 const double* lam_cell, const int* kp_bg, const int* kp_pos, const int* rowptr, const int* col, const double* A,
+                                 const double* M, const double* Dinv, const int* active, double tol, int max_iters, const double* dof_rest,
+                                 const double* rhs_rest, const double* rhs_gravity, const double* dof_f, double* dof, double* dof_vel, double* work,
+                                 double* pcg_work, int* stats, int mcadams_sweeps, void* stream);
 /* The local/global iterations of a substep as ONE persistent kernel of n_wg workgroups (one per CU; csrc/pn_sim_coop.h: k_substep_coop) instead of four
  * launches per iteration: same arguments and results as pn_sim_stepforward (tolerance of the summation orders, ~1e-13 relative), `work` prepared by
  * pn_sim_prepare, `coop` >= pn_sim_coop_bytes(n_k, n_IP, n_wg) bytes prepared by pn_sim_coop_prepare, which also returns plan[3] = {pieces, entries

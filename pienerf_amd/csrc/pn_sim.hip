@@ -19,6 +19,7 @@
 // here: k_update_F, k_matvec3 (every form's dense products) and, at the end, k_update_force, each with its op-level entry; between them the substep's forms:
 //   pn_sim_csr.h      launches over per-kernel CSR lists (k_elastic, the gathers, pn_sim_stepforward), calc_elastic / collect_rhs at op level
 //   pn_sim_cells.h    one launch per local/global iteration over kernel-grid cells (k_cells_elastic_gather, pn_sim_stepforward_cells)
+//   pn_sim_pcg.h      the cell form with the global step as a block-sparse PCG solve instead of the dense product (k_bsr_matvec3, k_pcg_*, pn_sim_stepforward_cells_pcg)
 //   pn_sim_coop.h     all iterations in one persistent kernel (k_substep_coop, pn_sim_stepforward_coop)
 #include <math.h>
 
@@ -138,6 +139,7 @@ extern "C" int pn_sim_matvec3(int n, const double* A, const double* X, double* Y
 // ------------------------------------------------------------------------------------------------ the three forms of the substep
 #include "pn_sim_csr.h"
 #include "pn_sim_cells.h"
+#include "pn_sim_pcg.h"
 #include "pn_sim_coop.h"
 
 // ------------------------------------------------------------------------------------------------ update_force

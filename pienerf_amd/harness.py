@@ -55,7 +55,8 @@ class SimRenderHarness:
         self.model.eval()
         # main_gui.py:39-48
         self.sim = Simulator(dt=o["sim_dt"], iters=o["sim_iters"], bbox=torch.tensor([2.0 * o["bound"]] * 3), dx=o["sim_dx"], stiff=o["sim_stiff"],
-                             base=torch.tensor([-o["bound"]] * 3), device=self.device)
+                             base=torch.tensor([-o["bound"]] * 3), device=self.device, kres=o.get("sim_kres", 7), solver=o.get("sim_solver", "dense"),
+                             pcg_tol=o.get("pcg_tol", 1e-10), pcg_max_iters=o.get("pcg_max_iters", 576))
         c = self.cloud
         self.sim.InitializeFromArrays(c["pos"], c["mass"], c["mu"], c["lam"], c["pin"])
         # main_gui.py:50-56

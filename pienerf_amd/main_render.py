@@ -74,6 +74,9 @@ def build_harness(args):
     opt = scene.default_opt(W=args.W, H=args.H, radius=args.radius, fovy=args.fovy, sim_dx=args.sim_dx, sim_iters=args.sim_iters,
                             max_iter_num=args.max_iter_num, num_seek_IP=args.num_seek_IP, bound=args.bound, dt_gamma=args.dt_gamma,
                             max_steps=args.max_steps, T_thresh=args.T_thresh, bg_radius=args.bg_radius)
+    # the simulator's kernel grid and global solve: keys the harness reads with their defaults, not part of scene.default_opt
+    opt.update(sim_kres=getattr(args, "sim_kres", 7), sim_solver=getattr(args, "sim_solver", "dense"), pcg_tol=getattr(args, "pcg_tol", 1e-10),
+               pcg_max_iters=getattr(args, "pcg_max_iters", 576))
     cloud = scene.cloud_from_ply(args.ply) if args.ply else None
     if args.unpin:   # every pin of the loaded cloud cleared: nothing holds the object (drop it onto --floor)
         cloud = dict(cloud if cloud is not None else scene.make_chair_points(hgs=opt["hash_grid_size"], bound=opt["bound"]))
@@ -454,6 +457,11 @@ def run(args):
     if h.sim.self_contact_enabled and not args.quiet:
         print(f"self-contact: {h.sim.self_contact_count()} of {h.sim.n_IP} integration points in contact with the body itself in the last substep, "
               f"{h.sim.self_contact_overflows()} substeps over the bucket cap")
+    if h.sim.solver == "pcg":   # printed whatever --quiet says: an unconverged solve is a result, not progress
+        st = h.sim.pcg_stats()
+        print(f"pcg: kres {h.sim.kres}, {h.sim.n_k} kernels ({int(h.sim.active_kernels.numel())} active), {int(h.sim.bsr_col.numel())} blocks; {st['solves']} solves, "
+              f"{st['unconverged']} unconverged columns; CG iterations in the last substep: max {st['iterations_max']}, "
+              f"mean {float(st['iterations'].mean()):.1f} per column (tol {h.sim.pcg_tol:g}, cap {h.sim.pcg_max_iters})")
     if not args.quiet:
         print(f"{done} frames -> {os.path.abspath(args.out)} in {time.time() - t0:.2f} s; last frame: {h.model.last_stats}")
     return written
@@ -480,6 +488,11 @@ def parser():
     ap.add_argument("--T_thresh", type=float, default=1e-2)
     ap.add_argument("--sim_dx", type=float, default=0.05)
     ap.add_argument("--sim_iters", type=int, default=10)
+    ap.add_argument("--sim_kres", type=int, default=7, help="GMLS kernels per axis of the simulator's kernel grid, >= 2 (the reference: 7); beyond 7 use --sim_solver pcg")
+    ap.add_argument("--sim_solver", choices=("dense", "pcg"), default="dense",
+                    help="the global step: the pre-inverted dense matrix, or a block-sparse preconditioned CG solve that builds no dense matrix (DESIGN.md 4.19)")
+    ap.add_argument("--pcg_tol", type=float, default=1e-10, help="--sim_solver pcg stops a column at |r| <= tol |b|")
+    ap.add_argument("--pcg_max_iters", type=int, default=576, help="--sim_solver pcg: CG iterations per solve at the most")
     ap.add_argument("--max_iter_num", type=int, default=1)
     ap.add_argument("--num_seek_IP", type=int, default=3)
     ap.add_argument("--force", type=float, nargs=3, default=None, help="constant force on one IP (gui.py drag), e.g. 300 100 -200")

@@ -170,6 +170,77 @@ def add_pin_penalty(mat, stiff, pin_ids, pts_topo, pts_Nx):
     return mat
 
 
+# ---------------------------------------------------------------------------------------------------- the same matrices in block-sparse rows
+# (Simulator(solver="pcg"): no [dim, dim] tensor anywhere.)  A block = the 10 x 10 coupling of one (row kernel, column kernel) pair; an integration point
+# couples the 8 kernels of its kernel-grid cell, so a row holds at most 27 blocks, 28 with a pinned point whose pts_kernel row names kernel 0.
+def bsr_pattern(n_k, IP_kernel, pin_rows):
+    """rowptr [n_k + 1], col [nnzb] (int32, columns ascending inside a row) of the union of all (row kernel, column kernel) pairs of every `IP_kernel` row,
+    of every pinned point's pts_kernel row `pin_rows` [n_pin, 8] (repeats included) and of the diagonal.  Symmetric by construction."""
+    dev = IP_kernel.device
+    rows = torch.unique(torch.cat([IP_kernel.long().reshape(-1, 8), pin_rows.long().reshape(-1, 8)], dim=0), dim=0)   # the points of a cell share one row
+    keys = [torch.arange(n_k, device=dev, dtype=torch.long) * (n_k + 1)]
+    for s in range(0, rows.shape[0], 65536):
+        r = rows[s:s + 65536]
+        keys.append(torch.unique((r[:, :, None] * n_k + r[:, None, :]).reshape(-1)))
+    keys = torch.unique(torch.cat(keys))                               # sorted: by row, then by column
+    cnt = torch.bincount(keys // n_k, minlength=n_k)
+    rowptr = torch.cat([torch.zeros(1, dtype=torch.long, device=dev), torch.cumsum(cnt, 0)])
+    return rowptr.to(torch.int32).contiguous(), (keys % n_k).to(torch.int32).contiguous()
+
+
+def bsr_keys(rowptr, col):
+    """row * n_k + col of every block, ascending: searchsorted on it finds a pair's block."""
+    n_k = rowptr.numel() - 1
+    row = torch.repeat_interleave(torch.arange(n_k, device=col.device), torch.diff(rowptr.long()))
+    return row * n_k + col.long()
+
+
+def _bsr_flat(keys, n_k, rows8):
+    """Flat index into [nnzb * 100] of every entry of the 80 x 80 blocks of points with kernels `rows8` [m, 8]: [m, 8, 10, 8, 10]."""
+    dev = rows8.device
+    want = rows8[:, :, None] * n_k + rows8[:, None, :]
+    bid = torch.searchsorted(keys, want.reshape(-1)).reshape(want.shape)
+    assert bool((keys[bid.clamp(max=keys.numel() - 1)] == want).all()), "a (row, column) pair is missing from the BSR pattern"
+    ar = torch.arange(10, device=dev)
+    return bid[:, :, None, :, None] * 100 + ar[None, None, :, None, None] * 10 + ar[None, None, None, None, :]
+
+
+def assemble_IP_bsr(rowptr, col, dx, dt, topo, mu, lam, rho, Nx, dNx, ddNx, chunk=512):
+    """assemble_IP_matrix's addends, chunked the same way, added into blocks [nnzb, 10, 10] of the pattern (rowptr, col) instead of a [dim, dim] matrix."""
+    dev = Nx.device
+    n, n_k = Nx.shape[0], rowptr.numel() - 1
+    keys = bsr_keys(rowptr, col)
+    out = torch.zeros(col.numel() * 100, dtype=F64, device=dev)
+    for s in range(0, n, chunk):
+        sl = slice(s, min(s + chunk, n))
+        m = sl.stop - sl.start
+        Z = torch.cat([Nx[sl].reshape(m, 1, 80), dNx[sl].permute(0, 2, 1, 3).reshape(m, 3, 80), ddNx[sl].permute(0, 2, 3, 1, 4).reshape(m, 9, 80)], dim=1)
+        c0 = rho[sl] * dx ** 3 / dt ** 2
+        c1 = dx ** 3 * (rho[sl] * dx ** 2 / 12.0 / dt ** 2 + mu[sl] + lam[sl])
+        c2 = dx ** 5 * (mu[sl] + lam[sl]) / 12.0
+        coef = torch.cat([c0[:, None], c1[:, None].expand(m, 3), c2[:, None].expand(m, 9)], dim=1)   # [m,13]
+        blocks = torch.einsum("vr,vra,vrb->vab", coef, Z, Z)                                            # [m,80,80]
+        index_add_ordered(out, _bsr_flat(keys, n_k, topo[sl].long()).reshape(-1), blocks.reshape(-1))
+    return out.view(-1, 10, 10)
+
+
+def add_pin_penalty_bsr(blocks, rowptr, col, stiff, pin_ids, pts_topo, pts_Nx):
+    """add_pin_penalty's addends (stiff * N N^T per pinned point, repeated kernels adding up) into the blocks."""
+    if pin_ids.numel() == 0:
+        return blocks
+    n_k = rowptr.numel() - 1
+    nv = pts_Nx[pin_ids].reshape(-1, 80)
+    flat = _bsr_flat(bsr_keys(rowptr, col), n_k, pts_topo[pin_ids].long())
+    index_add_ordered(blocks.view(-1), flat.reshape(-1), (stiff * nv[:, :, None] * nv[:, None, :]).reshape(-1))
+    return blocks
+
+
+def bsr_diagonal(rowptr, col):
+    """[n_k] the block index of every kernel's diagonal block."""
+    n_k = rowptr.numel() - 1
+    return torch.searchsorted(bsr_keys(rowptr, col), torch.arange(n_k, device=col.device) * (n_k + 1))
+
+
 def inverse_spd(mat):
     """Dense fp64 inverse of the system block (solver.py:508: `.inverse()`, an LU).  The block is symmetric positive definite (mass + stiffness +
     pin penalty + 1e-3 I), so it is factored as L L^T and inverted from the factor (half the work of the LU, a symmetric result); LU if the

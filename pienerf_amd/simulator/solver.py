@@ -6,6 +6,8 @@ Kept: constructor arguments, ``InitializeFromPly``, ``get_IP_info`` (fp32, permu
   * the per-substep work is HIP (libpienerf_hip.so: pn_sim_stepforward / pn_sim_update_F / pn_sim_update_force);
   * ``global_matrix`` / ``mass_matrix_invt2`` are stored in their kron(A, I3) factor form ``Ainv`` / ``Mmat``
     ([10 n_k]^2 instead of [30 n_k]^2, solver.py:493-496,532-538) — same products, 9x fewer bytes;
+  * ``Simulator(solver="pcg")`` builds neither: the system stays in block-sparse rows (``bsr_*``) and every global step is a block-Jacobi PCG solve
+    (csrc/pn_sim_pcg.h, DESIGN.md 4.19), for kernel grids (``kres`` > 7) whose dense inverse does not fit;
   * importing this module does not call ``torch.set_default_device("cuda")`` (func_utils.py:6).
 """
 import contextlib
@@ -44,8 +46,20 @@ class Simulator(StageHost, DragMixin, PinsMixin, ContactMixin, BodiesMixin, Fiel
 
     def __init__(self, dt=1e-2, iters=20, bbox=torch.tensor([1.0, 1.0, 1.0], dtype=torchfloat), kres=7, dx=1,
                  gravity=torch.tensor([0.0, -9.8, 0.0], dtype=torchfloat), stiff=1e5, base=torch.tensor([-0.5, -0.5, -0.5], dtype=torchfloat),
-                 device="cuda", persistent=None, svd=None):
+                 device="cuda", persistent=None, svd=None, solver="dense", pcg_tol=1e-10, pcg_max_iters=576):
         self.device = torch.device(device)
+        # solver: how the global step applies the inverse of the system block (solver.py:505-511,600).  "dense" (default): the pre-inverted [10 n_k]^2
+        # matrix, one product per local/global iteration — right at the reference's kres = 7.  "pcg": the block stays in block-sparse rows and every
+        # iteration solves with it by block-Jacobi conjugate gradients (csrc/pn_sim_pcg.h) to |r| <= pcg_tol |b|, at most pcg_max_iters iterations: no
+        # [dim, dim] tensor is ever built, which is what lets kres grow.  On the cell form only.
+        if solver not in ("dense", "pcg"):
+            raise ValueError(f"Simulator: solver must be 'dense' or 'pcg', got {solver!r}")
+        if int(kres) < 2:
+            raise ValueError(f"Simulator: kres must be at least 2 (the kernel grid spans the box with kres - 1 cells), got {kres!r}")
+        if solver == "pcg" and (not float(pcg_tol) >= 0.0 or int(pcg_max_iters) < 1):
+            raise ValueError("Simulator: pcg_tol must be >= 0 and pcg_max_iters >= 1")
+        self.solver, self.pcg_tol, self.pcg_max_iters = solver, float(pcg_tol), int(pcg_max_iters)
+        self._pcg_work = self._pcg_stats = None
         # svd: which decomposition stands in for wp.svd3 (cuda_utils.py:107) in calc_elastic.  "jacobi" (default): the converged, warm-started threshold
         # Jacobi; "mcadams" / "mcadams:N": the published algorithm wp.svd3 implements (McAdams et al., TR1690) with N fixed sweeps (default 8, the setting
         # of double-precision builds; 4 is the paper's single-precision setting) — csrc/pn_sim_svd.h: svd3_mcadams.  None: environment PN_SIM_SVD.
@@ -64,10 +78,14 @@ class Simulator(StageHost, DragMixin, PinsMixin, ContactMixin, BodiesMixin, Fiel
         self.persistent = bool(persistent)
         if self.persistent and self.svd_sweeps:
             raise ValueError("Simulator: the persistent substep has the default decomposition only; svd='mcadams' runs on the cell and CSR forms")
+        if self.persistent and solver == "pcg":
+            raise ValueError("Simulator: solver='pcg' runs on the cell form; the persistent substep multiplies by the dense inverse")
         self._coop = None
         # cell_form: calc_elastic + collect_rhs_IP of a local/global iteration as one launch per kernel-grid cell chunk (pn_sim_stepforward_cells, 21
         # launches per substep instead of 31); PN_SIM_FORM=csr keeps the round-1-4 launch form (three launches per iteration over per-kernel CSR lists)
         self.cell_form = os.environ.get("PN_SIM_FORM", "cells") != "csr"
+        if not self.cell_form and solver == "pcg":
+            raise ValueError("Simulator: solver='pcg' runs on the cell form; PN_SIM_FORM=csr multiplies by the dense inverse")
         bbox = bbox.clone() * 1.02   # solver.py:24-25 multiply in the caller's dtype (main_gui.py passes float32), then widen
         base = base.clone() * 1.01
         self.dt, self.iters, self.dx, self.kres, self.stiff = dt, iters, dx, kres, stiff
@@ -116,7 +134,10 @@ class Simulator(StageHost, DragMixin, PinsMixin, ContactMixin, BodiesMixin, Fiel
         self.precompute()
         self._work = torch.empty(int(lib().pn_sim_work_doubles(self.n_k, self.n_IP)), dtype=torchfloat, device=self.device)
         self._prepared = False
-        self.rhs_rest = (self.build_rhs() + self._matvec(self.Mmat, self.dof)).contiguous()   # solver.py:314
+        if self.solver == "pcg":
+            self._pcg_work = torch.empty(int(lib().pn_sim_pcg_work_doubles(self.n_k)), dtype=torchfloat, device=self.device)
+            self._pcg_stats = torch.zeros(2 + 6 * max(int(self.iters), 1), dtype=torch.int32, device=self.device)
+        self.rhs_rest = (self.build_rhs() + (self._bsr_matvec(self.bsr_M, self.dof) if self.solver == "pcg" else self._matvec(self.Mmat, self.dof))).contiguous()   # solver.py:314
         for st in self.enabled_stages() if self.device.type == "cuda" else ():
             getattr(self, st.alloc)()
 
@@ -271,6 +292,8 @@ class Simulator(StageHost, DragMixin, PinsMixin, ContactMixin, BodiesMixin, Fiel
         return (s_mu / s_m).contiguous(), (s_lam / s_m).contiguous(), (s_m / (self.dx ** 3)).contiguous()
 
     def build_global(self):  # solver.py:453-538
+        if self.solver == "pcg":
+            return self._build_global_bsr()
         dim = self.n_k * 10
         mat = gmls.assemble_IP_matrix(dim, self.dx, self.dt, self.IP_kernel, self.IP_mu, self.IP_lam, self.IP_rho, self.IP_Nx, self.IP_dNx, self.IP_ddNx)
         assert self.pts_kernel.min() >= 0 and self.pts_kernel.max() < self.n_k
@@ -287,6 +310,48 @@ class Simulator(StageHost, DragMixin, PinsMixin, ContactMixin, BodiesMixin, Fiel
         self.Ainv = self.Ainv.contiguous()
         zero = torch.zeros_like(self.IP_mu)
         self.Mmat = gmls.assemble_IP_matrix(dim, self.dx, self.dt, self.IP_kernel, zero, zero, self.IP_rho, self.IP_Nx, self.IP_dNx, self.IP_ddNx).contiguous()
+
+    def _build_global_bsr(self):
+        """build_global() for solver='pcg': the system block A (+1e-3 on the active kernels' diagonal, :507) and the mass block M in block-sparse rows
+        on one pattern, the active kernels by the dense path's rule, and the inverted diagonal blocks the solve is preconditioned with."""
+        dev, n_k = self.device, self.n_k
+        assert self.pts_kernel.min() >= 0 and self.pts_kernel.max() < n_k
+        vid = torch.nonzero(self.is_pin).reshape(-1)
+        self.bsr_rowptr, self.bsr_col = gmls.bsr_pattern(n_k, self.IP_kernel, self.pts_kernel[vid])
+        args = (self.IP_rho, self.IP_Nx, self.IP_dNx, self.IP_ddNx)
+        A = gmls.assemble_IP_bsr(self.bsr_rowptr, self.bsr_col, self.dx, self.dt, self.IP_kernel, self.IP_mu, self.IP_lam, *args)
+        A = gmls.add_pin_penalty_bsr(A, self.bsr_rowptr, self.bsr_col, self.stiff, vid, self.pts_kernel, self.pts_Nx)
+        diag = gmls.bsr_diagonal(self.bsr_rowptr, self.bsr_col)
+        on = A[diag, 0, 0] > 0.0                                                           # `global_matrix[i*30, i*30] > 0` (:499-504)
+        self.active_kernels = torch.nonzero(on).reshape(-1)
+        self.bsr_active = on.to(torch.int32).contiguous()
+        A[diag[on]] += 1e-3 * torch.eye(10, dtype=torchfloat, device=dev)                  # :507
+        self.bsr_Dinv = torch.zeros((n_k, 10, 10), dtype=torchfloat, device=dev)
+        self.bsr_Dinv[on] = torch.linalg.inv(A[diag[on]])
+        self.bsr_A = A.contiguous()
+        zero = torch.zeros_like(self.IP_mu)
+        self.bsr_M = gmls.assemble_IP_bsr(self.bsr_rowptr, self.bsr_col, self.dx, self.dt, self.IP_kernel, zero, zero, *args).contiguous()
+
+    def __getattr__(self, name):   # (only reached when the attribute is not there)
+        if name in ("Ainv", "Mmat") and self.__dict__.get("solver") == "pcg":
+            raise RuntimeError(f"Simulator(solver='pcg') builds no dense matrix: {name}, global_matrix and mass_matrix_invt2 exist with solver='dense' "
+                                 "only; the block-sparse system is bsr_rowptr / bsr_col / bsr_A / bsr_M")
+        raise AttributeError(f"{type(self).__name__!r} object has no attribute {name!r}")
+
+    def _bsr_matvec(self, blocks, x):
+        y = torch.empty_like(x)
+        check(lib().pn_sim_bsr_matvec3(self.n_k, ptr(self.bsr_rowptr), ptr(self.bsr_col), ptr(blocks), ptr(x), ptr(y), stream_ptr()), "sim_bsr_matvec3")
+        return y
+
+    def pcg_stats(self):
+        """Statistics of the PCG global solves (one synchronous read): `solves` and `unconverged` (columns that stopped at pcg_max_iters or broke down),
+        running totals since initialize(); `iterations` [iters, 3], the CG iterations of each local/global iteration's three columns in the last
+        substep, and `iterations_max`, the largest of them."""
+        if self.solver != "pcg" or self._pcg_stats is None:
+            raise RuntimeError("Simulator.pcg_stats: solver='pcg' on an initialised GPU simulator only")
+        st = self._pcg_stats.cpu().numpy()
+        it = st[2:].reshape(-1, 6)[:int(self.iters), :3].copy()   # (the buffer is sized by iters at initialize(); a later, smaller iters writes fewer rows)
+        return dict(solves=int(st[0]), unconverged=int(st[1]), iterations=it, iterations_max=int(it.max()) if it.size else 0)
 
     # the reference's (30 n_k)^2 forms, materialised on demand (tests / interop only)
     @property
@@ -350,7 +415,7 @@ class Simulator(StageHost, DragMixin, PinsMixin, ContactMixin, BodiesMixin, Fiel
         """Switch to the persistent substep (a harness calls this for a GPU that only simulates: the owner rank of a frame-parallel job with a
         dedicated simulator).  PN_SIM_COOP=0 vetoes it, so does svd='mcadams' (the persistent form has the default decomposition only); scenes that
         do not fit keep the launch form.  Returns whether it is on."""
-        if os.environ.get("PN_SIM_COOP", "") == "0" or self.svd_sweeps:
+        if os.environ.get("PN_SIM_COOP", "") == "0" or self.svd_sweeps or self.solver == "pcg":
             return False
         self.persistent = True
         if self._prepared and self._coop is None:
@@ -390,11 +455,23 @@ class Simulator(StageHost, DragMixin, PinsMixin, ContactMixin, BodiesMixin, Fiel
             if self._cells_work is None:
                 raise RuntimeError("Simulator: the cell form's work area is missing (precompute() prepares it on a GPU device)")
             c = self._cells
+            if self.solver == "pcg":
+                if self._pcg_stats.numel() < 2 + 6 * int(self.iters):
+                    raise RuntimeError("Simulator: iters grew since initialize(); the PCG statistics hold one row per local/global iteration")
+                check(lib().pn_sim_stepforward_cells_pcg(self.n_k, c["n_chunks"], int(self.iters), float(self.dt), float(self.dx), ptr(c["tab"]), ptr(c["dNx"]),
+                                                         ptr(c["mu"]), ptr(c["lam"]), ptr(c["kp_bg"]), ptr(c["kp_pos"]), ptr(self.bsr_rowptr), ptr(self.bsr_col),
+                                                         ptr(self.bsr_A), ptr(self.bsr_M), ptr(self.bsr_Dinv), ptr(self.bsr_active), self.pcg_tol,
+                                                         self.pcg_max_iters, ptr(self.dof_rest), ptr(self.rhs_rest), ptr(rhs_g), ptr(self.dof_f), ptr(self.dof),
+                                                         ptr(self.dof_vel), ptr(self._cells_work), ptr(self._pcg_work), ptr(self._pcg_stats), self.svd_sweeps,
+                                                         stream_ptr()), "stepforward_cells_pcg")
+                return
             check(lib().pn_sim_stepforward_cells(self.n_k, c["n_chunks"], int(self.iters), float(self.dt), float(self.dx), ptr(c["tab"]), ptr(c["dNx"]),
                                                  ptr(c["mu"]), ptr(c["lam"]), ptr(c["kp_bg"]), ptr(c["kp_pos"]), ptr(self.Ainv), ptr(self.Mmat),
                                                  ptr(self.dof_rest), ptr(self.rhs_rest), ptr(rhs_g), ptr(self.dof_f), ptr(self.dof), ptr(self.dof_vel),
                                                  ptr(self._cells_work), self.svd_sweeps, stream_ptr()), "stepforward_cells")
             return
+        if self.solver == "pcg":
+            raise RuntimeError("Simulator: solver='pcg' runs on the cell form with iters >= 1 (cell_form was switched off after construction)")
         check(lib().pn_sim_stepforward(self.n_k, self.n_IP, int(self.iters), float(self.dt), float(self.dx), ptr(self.IP_kernel), ptr(self.kernel_bg),
                                        ptr(self.kernel_cnt), ptr(self.buffer), ptr(self.IP_mu), ptr(self.IP_lam), ptr(self.IP_dNx), ptr(self.dNx_csr), ptr(self.csr_pos), ptr(self.Ainv),
                                        ptr(self.Mmat), ptr(self.dof_rest), ptr(self.rhs_rest), ptr(rhs_g), ptr(self.dof_f), ptr(self.dof),
