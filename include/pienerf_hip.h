@@ -394,7 +394,9 @@ int pn_render_continue(pn_frame* f, const pn_net* net, const pn_render_opts* opt
  * aabb_infer], trips of { march_rays, network, composite_rays, compaction } with the same device-side trip record as pn_render_deformed, then
  * image += (1 - weights_sum) * bg, depth = clamp(depth - nears, 0) / (fars - nears).  n_trips == 0: blocking form (batches of trips
  * until no ray is alive); n_trips > 0: exactly that many trips, no host synchronisation (pn_render_status afterwards).  depth_0 receives the
- * un-normalised depth (the reference discards it).  Off the simulate-and-render hot path. */
+ * un-normalised depth (the reference discards it).  "Rays alive at exit" of a static frame (stats[3]) also counts the rays that max_steps ended the loop
+ * on, as NeRFRenderer.run_cuda_ops reports them: more trips do nothing for those (pn_render_continue leaves the frame as it is) and they are not
+ * added to the unfinished total.  The deformed forms report 0 there.  Off the simulate-and-render hot path. */
 int pn_render_static(pn_frame* f, const pn_net* net, const pn_render_opts* opts, const float* rays_o, const float* rays_d, uint32_t N,
                      const float* aabb_host, const uint8_t* bitfield, float* image, float* depth, float* depth_0, float* weights_sum,
                      int64_t* stats_host, int n_trips, void* stream);

@@ -109,6 +109,8 @@ __device__ __forceinline__ void trip_epilogue(int lane, int sum, PnTrip* trip, P
         next->dense = dense ? 1 : 0;
         next->n_samples = dense ? sum * next->n_step : 0;
         next->n_emitted = 0;
+        // the rays max_steps ended the loop on (renderer.py:836 leaves them alive); an empty trip hands on what it found in its own record
+        next->n_left = sum > 0 ? (done ? sum : 0) : trip->n_left;
     }
 }
 

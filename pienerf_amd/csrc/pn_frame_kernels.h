@@ -79,11 +79,13 @@ __global__ void k_reset_unfinished(PnFrameDev* dev) { dev->unfinished = 0; }
 
 // image = acc + (1 - weights_sum) * bg ; depth = clamp(depth - nears, 0) / (fars - nears) (renderer.py:896-899)
 // The first wave of the launch also closes the frame's books: trips_run (+ the trips a fused launch ran, whose number only the device knows), the summary
-// of the trip records (what pn_render_status reports) and the rays a fixed-trip render left alive.
+// of the trip records (what pn_render_status reports) and the rays a fixed-trip render left alive.  count_left (the static render): alive_at_exit also
+// counts the rays max_steps ended the loop on (PnTrip::n_left), as the op-by-op loop run_cuda_ops reports them; more trips do nothing for those, so they
+// are not `unfinished`.  (The deformed frame's fused launch does not know that count, so none of the deformed forms reports it.)
 __global__ void __launch_bounds__(256) k_frame_finish(uint32_t N, float bg, const float* __restrict__ nears, const float* __restrict__ fars,
                                                       const float* __restrict__ weights_sum, const float* __restrict__ depth_0,
                                                       const float* __restrict__ acc, float* __restrict__ image, float* __restrict__ depth,
-                                                      const PnTrip* __restrict__ trips, PnFrameDev* dev, int trips_run, int add_fused) {
+                                                      const PnTrip* __restrict__ trips, PnFrameDev* dev, int trips_run, int add_fused, int count_left) {
     const uint32_t i = threadIdx.x + blockIdx.x * blockDim.x;
     if (i < 64) {
         const int lane = (int)i;
@@ -103,7 +105,7 @@ __global__ void __launch_bounds__(256) k_frame_finish(uint32_t N, float bg, cons
             dev->fused_trips = 0;
             dev->stat_trips = n_trips;
             dev->stat_samples = n_samples;
-            dev->alive_at_exit = left;
+            dev->alive_at_exit = left + (count_left ? trips[t_final].n_left : 0);
             if (left > 0) atomicAdd(&dev->unfinished, left);
         }
     }

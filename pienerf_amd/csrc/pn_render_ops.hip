@@ -705,7 +705,8 @@ static int render_impl(pn_frame* f, const pn_net* net, const pn_render_opts* o, 
     bool finished_in_launch = false;
     if ((rc = enqueue_trips(c, pl, async_trips, resume, t, add_fused, finished_in_launch))) return rc;
     if (!finished_in_launch)
-        k_frame_finish<<<pl.nblk, 256, 0, c.st>>>(N, o->bg_color, f->nears, f->fars, weights_sum, depth_0, f->acc_image, image, depth, f->trips, f->dev, t, add_fused);
+        k_frame_finish<<<pl.nblk, 256, 0, c.st>>>(N, o->bg_color, f->nears, f->fars, weights_sum, depth_0, f->acc_image, image, depth, f->trips, f->dev, t, add_fused,
+                                                  pl.is_static ? 1 : 0);
     PN_LAUNCH_CHECK();
     f->last_trips = t;
     f->last_N = N;

@@ -10,7 +10,9 @@ struct PnTrip {
     int n_step;     // max(min(N // n_alive, 8), 1)
     int step_base;  // renderer's `step` before this trip
     int dense;      // see below
-    int pad0[28];
+    int n_left;     // rays the loop ended on: alive behind the trip that took `step` to max_steps (renderer.py:836), carried through the empty
+                    // trips behind it; 0 while the loop goes on or when it ended because no ray was left (n_alive is 0 in both cases)
+    int pad0[27];
     // counters the march updates with atomics: a cache line of their own, so that the waves reading the fields above (every wave's first
     // instruction) do not queue behind them
     int n_samples;  // entries of the sample list the network kernel reads (list trips: filled by atomics; dense trips: n_alive * n_step)
@@ -58,7 +60,7 @@ struct PnFrameDev {
     int fused_trips;    // trips the last k_trips_fused launch ran (pn_trips_fused.h); k_frame_finish adds them to trips_run and clears the field
     // summary of the trip records, written by k_frame_finish (the host reads this record instead of every trip's):
     int stat_trips;     // trips that had rays
-    int alive_at_exit;  // rays alive behind the last trip enqueued
+    int alive_at_exit;  // rays alive behind the last trip enqueued (the static render: + the rays max_steps ended the loop on, PnTrip::n_left)
     int pad0;
     long long stat_samples;  // samples marched (dense trips: emitted; list trips: listed)
     // cells [ip_lo, ip_hi] per axis hold every integration point (k_frame_tables); with --cut the search grid spans +-bound (67^3 cells on the trex option

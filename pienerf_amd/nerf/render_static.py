@@ -45,7 +45,9 @@ class StaticRenderMixin:
         o = self._static_opts(dt_gamma, bg_color, max_steps, T_thresh)
         aabb = (C.c_float * 6)(*self._aabb_infer_host())
         image, depth, depth_0, ws = frame_outputs(N, device)
-        frame = self._frame_handle(N, 1, 1.0, int(kwargs.get("frame_slot") or 0), cells=1)
+        slot = int(kwargs.get("frame_slot") or 0)
+        frame = self._frame_handle(N, 1, 1.0, slot, cells=1)
+        self._static_depth_0[slot] = depth_0   # render_continue(static=True) composites on into it
         async_trips = int(kwargs.get("async_trips") or 0)
         stats = (C.c_int64 * 5)() if not async_trips else None
         check(lib().pn_render_static(frame, self._net_handle(half=bool(o.fp16)), C.byref(o), ptr(rays_o), ptr(rays_d), N, aabb, ptr(self.density_bitfield),

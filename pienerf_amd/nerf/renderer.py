@@ -74,6 +74,8 @@ class NeRFRenderer(ColliderOverlayMixin, PointOverlayMixin, StaticRenderMixin, H
             self.local_step = 0
         self._frames = {}              # frame workspaces: slot -> (pn_frame handle, what it was sized for)
         self._aabb_cache = (None, None)   # _aabb_infer_host: (the buffer's address and version, its six floats)
+        self._static_depth_0 = {}      # slot -> the un-normalised depth of the static frame last rendered there: run_cuda returns the reference's three
+                                       # tensors, and a continuation composites on into this fourth
         self.last_stats = None
         self._overlay = None   # set_collider_overlay: a ColliderOverlay
         self._shadows = None   # set_collider_shadows: a ColliderShadows
@@ -259,7 +261,14 @@ class NeRFRenderer(ColliderOverlayMixin, PointOverlayMixin, StaticRenderMixin, H
         # with an overlay the epilogue rewrites `image` from the driver's accumulator over 0 and the layers are applied once more, below
         o = self._static_opts(dt_gamma, bg_driver, max_steps, T_thresh) if static else self._deformed_opts(dt_gamma, bg_driver, max_steps, T_thresh, kwargs, n_rays=N)
         image, depth, ws = out["image"].view(-1, 3), out["depth"].view(-1), out["weights_sum"].view(-1)
-        depth_0 = out["depth_0"].view(-1) if "depth_0" in out else torch.empty_like(depth)
+        if "depth_0" in out:
+            depth_0 = out["depth_0"].view(-1)
+        elif static:   # the accumulator the composite goes on adding to: the frame's own, never a new tensor
+            depth_0 = self._static_depth_0.get(slot)
+            if depth_0 is None or depth_0.shape != depth.shape or depth_0.device != depth.device:
+                raise RuntimeError(f"render_continue: no static frame of {N} rays was rendered on frame workspace {slot}")
+        else:
+            depth_0 = torch.empty_like(depth)
         assert image.is_contiguous() and image.shape[0] == N
         stats = (C.c_int64 * 5)() if int(n_trips) == 0 else None
         check(lib().pn_render_continue(self._frames[slot][0], self._net_handle(half=bool(o.fp16)), C.byref(o), ptr(rays_o), ptr(rays_d), N,
@@ -286,7 +295,8 @@ class NeRFRenderer(ColliderOverlayMixin, PointOverlayMixin, StaticRenderMixin, H
 
     def render_status(self, synchronize=True, slot=0):
         """Outcome of the last render on frame workspace `slot`: dict(trips, samples, err, alive_at_exit).
-        After an async render, alive_at_exit > 0 means the enqueued trips were not enough."""
+        After an async render, alive_at_exit > 0 means the enqueued trips were not enough — or, on a static frame (run_cuda), that max_steps
+        ended the loop with that many rays alive, as run_cuda_ops reports it; render_continue leaves such a frame as it is."""
         stats = (C.c_int64 * 5)()
         check(lib().pn_render_status(self._frames[slot][0], stats, int(bool(synchronize)), stream_ptr()), "render_status")
         self._set_stats(stats)
