@@ -652,13 +652,20 @@ int pn_sim_pins_rhs(int n_k, int n_pin, void* state, double dt, double stiff, co
  *     rhs_out[k 30 + j 3 + r] = rhs_in[...] + sum_e m_i Nx[i,slot,j] a_i[r]  over the (i, slot) entries e of kernel k's run, ascending.
  * The system matrix is at least M / dt^2, so a point's response to its own term is at most dt^2 a_n <= (kappa + beta) delta.  Layout of the state: */
 #define PN_CONTACT_SLOTS 8
-enum { PN_CONTACT_EMPTY = 0, PN_CONTACT_PLANE = 1, PN_CONTACT_SPHERE = 2, PN_CONTACT_CONTAINER = 3 };
+enum { PN_CONTACT_EMPTY = 0, PN_CONTACT_PLANE = 1, PN_CONTACT_SPHERE = 2, PN_CONTACT_CONTAINER = 3, PN_CONTACT_BOX = 4, PN_CONTACT_CAPSULE = 5 };
+/* The two solid primitives in the same slot, distance and normal as the law above takes them:
+ *     box (axis-aligned; p the centre, n the three half-extents, each > 0, R exactly 0 — reserved):  r = x - p, q_i = |r_i| - n_i, sgn(r_i) = +1 for
+ *         r_i >= 0, else -1.  max_i q_i > 0 (outside): e_i = max(q_i, 0), d = sqrt(e.e), nh_i = sgn(r_i) e_i / d — the Euclidean distance, with face,
+ *         edge and corner regions.  Otherwise (inside or on the surface): k the axis of the largest q_i (lowest index on ties), d = q_k <= 0,
+ *         nh = sgn(r_k) times unit axis k.
+ *     capsule (p the end point A, n = B - A with n.n > 0, not normalised, R > 0):  s = clamp(((x - p).n) / (n.n), 0, 1), c = p + s n, then the sphere's
+ *         rule with centre c and radius R (its fallback normal (0, 1, 0) when x == c). */
 typedef struct pn_contact_collider {
     int type;          /* PN_CONTACT_*; 0: the slot is empty */
     int reserved;
-    double p[3];       /* a point of the plane / the sphere's centre */
-    double n[3];       /* the plane's unit normal, out of the solid */
-    double R;          /* the sphere's radius */
+    double p[3];       /* a point of the plane / the sphere's centre / the box's centre / the capsule's end point A */
+    double n[3];       /* the plane's unit normal, out of the solid / the box's half-extents / the capsule's B - A */
+    double R;          /* the sphere's or capsule's radius; a box: 0 */
     double v[3];       /* the collider's velocity */
 } pn_contact_collider;
 typedef struct pn_contact_state {
@@ -675,7 +682,7 @@ uint64_t pn_sim_contact_bytes(void);     /* sizeof(pn_contact_state) = 744 */
  * mu >= 0, h >= 0, else PN_ERR_ARG.  A one-thread launch on `stream`. */
 int pn_sim_contact_set_params(void* state, int active, const double* params4_host, void* stream);
 /* Writes slot `index` (0 .. 7) and recomputes n.  geom10_host = (p[3], n[3], R, v[3]), finite; a plane's normal is a unit vector to 1e-9, a sphere's
- * or container's R > 0, else PN_ERR_ARG; type PN_CONTACT_EMPTY clears the slot (geom10_host may be NULL).  A one-thread launch on `stream`. */
+ * or container's R > 0, a box's half-extents > 0 and its R exactly 0, a capsule's n.n > 0 and R > 0, else PN_ERR_ARG; type PN_CONTACT_EMPTY clears the slot (geom10_host may be NULL).  A one-thread launch on `stream`. */
 int pn_sim_contact_set_collider(void* state, int index, int type, const double* geom10_host, void* stream);
 /* rhs_out [10 n_k,3] = rhs_in + the contact term; rhs_in is left untouched and rhs_out is another buffer.  topo [n_IP,8], rho [n_IP], Nx [n_IP,8,10];
  * kernel_bg / kernel_cnt [n_k] and buffer [8 n_IP] (entry = point 8 + slot) the per-kernel CSR of pn_sim_stepforward, Nx_csr [8 n_IP,10] the Nx rows in
@@ -709,9 +716,9 @@ int pn_sim_accel_rhs(int n_k, int n_IP, double dx, const double* rho, const int*
  *      the device.
  *   3. clamp: s = min(1, M delta_max / (dt^2 |F_b|)) (s = 1 when F_b = 0), so the body's own response dt^2 s |F_b| / M to its reaction is at most
  *      its deepest penetration: the counterpart of dt^2 a_n <= (kappa + beta) delta for a point.  A (substep, body) pair with s < 1 is counted.
- *   4. static colliders: every other slot that is not a dynamic body (planes, solid spheres, the container) acts on the ball through the same law,
+ *   4. static colliders: every other slot that is not a dynamic body (planes, solid spheres, the container, boxes, capsules) acts on the ball through the same law,
  *      applied at the point p with velocity u and the ball's radius in the thickness's place (kappa, beta, mu of the contact state; velocity relative
- *      to that collider's v): plane d = n.(p - p_c) - R, solid sphere d = |p - p_c| - R_c - R, container d = R_c - |p - p_c| - R, delta = max(-d, 0),
+ *      to that collider's v): plane d = n.(p - p_c) - R, solid sphere d = |p - p_c| - R_c - R, container d = R_c - |p - p_c| - R, box and capsule d = (their distance at p) - R, delta = max(-d, 0),
  *      slots in index order, giving a_static.  Static colliders get no reaction; two dynamic balls pass through each other.
  *   5. integration, semi-implicit like the object's: u+ = (u + dt (g + s F_b / M + a_static)) / (1 + dt c), p+ = p + dt u+, both written into the
  *      slot; the substep clock k advances.
@@ -926,9 +933,22 @@ uint64_t pn_sim_diagnostics_work_doubles(int n_IP);
  *     sphere (c, R):     oc = o - c, b = oc.d, disc = b b - q (oc.oc - R R);  hit iff disc > 0;  t = (-b - sqrt(disc)) / q if that is > t_min, else
  *                        (-b + sqrt(disc)) / q;  then t in (t_min, t_max);  normal (x - c) / R, x = o + t d
  *     container (c, R):  the larger root only (the inner wall seen through the front: a camera outside still sees the object);  normal -(x - c) / R
+ *     box (c, h):        the three slabs in axis order.  d_i == 0: the ray misses unless |o_i - c_i| < h_i, and the axis bounds nothing.  Else
+ *                        t1 = ((c_i - h_i) - o_i) / d_i, t2 = ((c_i + h_i) - o_i) / d_i;  t_enter = the largest min(t1, t2), t_exit = the smallest
+ *                        max(t1, t2), each with the axis that gave it (the lowest index on ties);  hit iff t_enter < t_exit;  t = t_enter if that is
+ *                        > t_min, else t_exit (the eye inside: the far face);  then t in (t_min, t_max);  normal: the chosen end's axis
+ *     capsule (A, n, R): a = n / |n|, len = |n|, B = A + n, once per workgroup (|n| = 0 in fp32: the sphere (A, R)).  The convex union of three
+ *                        parts, each an interval (near, far):  the spheres (A, R) and (B, R) with the sphere's roots, disc > 0;  the cylinder, with
+ *                        oc = o - A, ad = a.d, ao = a.oc, dp = d - ad a, op = oc - ao a, A2 = dp.dp, b = op.dp, disc = b b - A2 (op.op - R R):  hit iff
+ *                        A2 > 0 and disc > 0, (near, far) = ((-b - sqrt(disc)) / A2, (-b + sqrt(disc)) / A2) intersected with the slab between the
+ *                        end planes — ad == 0: kept iff 0 < ao < len;  else s1 = (0 - ao) / ad, s2 = (len - ao) / ad, near = max(near, min(s1, s2)),
+ *                        far = min(far, max(s1, s2)) — and kept iff near < far.  t_near = the smallest near, t_far = the largest far over the parts
+ *                        that are hit;  t = t_near if that is > t_min, else t_far;  then t in (t_min, t_max);  normal (x - c) / R with
+ *                        c = A + clamp(a.(x - A), 0, len) a, evaluated as ((x - A) - clamp(..) a) / R
  * Colour of the hit slot k:  shade = ambient + (1 - ambient) |normal.d| / sqrt(q);  for a plane with checker > 0: u = normalised nh x e, e the
  * coordinate axis on which |nh| is smallest (lowest index on ties), v = nh x u, parity = (floor(u.(x - p) / checker) + floor(v.(x - p) / checker)) & 1,
- * factor = checker_dim for parity 1, else 1;  c = (rgb[k] factor) shade.
+ * factor = checker_dim for parity 1, else 1;  c = (rgb[k] factor) shade.  A box's face carries the same checker over the two world axes other than
+ * the face's, in index order (i < j): parity = (floor((x - c)_i / checker) + floor((x - c)_j / checker)) & 1.
  * Fade: a = clamp((t_max - t) / (0.5 t_max), 0, 1) — an endless floor dissolves into the background instead of ending at a line.
  * Composite, with s = weights_sum[i], acc = image[i] on entry (the frame composited over 0), t_obj = depth_0[i] / s when s > 1e-4, else +inf:
  *     no hit    : out = acc                    cov = s
@@ -966,12 +986,15 @@ int pn_draw_colliders(const void* contact_state, const pn_collider_style* style,
  *     occ_map = clamp(sum, 0, 1)
  *     with spheres != 0, every valid slot k' != k holding a solid sphere (c', R):  oc = x - c', b = oc.L, disc = b b - (oc.oc - R R);  it blocks the
  *     light iff disc > 0 and -b + sqrt(disc) > 0;  occ_sph = 1 if any blocks, else 0.  Planes and the container cast nothing.
+ *     Likewise every valid slot k' != k holding a box or a capsule: with the intervals of pn_draw_colliders for the ray (o, d) = (x, L), q = L.L, a
+ *     box blocks the light iff t_enter < t_exit and t_exit > 0, a capsule iff a part is hit and t_far > 0 (the ray x + s L, s > 0, passes through
+ *     the solid);  a blocker sets occ_sph = 1.
  *     occ = max(occ_map, occ_sph);  the slot's colour c of pn_draw_colliders becomes c (1 - strength occ), per component;  shadow_out[i] = occ
  * The composite, coverage_out and collider_t_out are pn_draw_colliders' own, and so is a ray without a hit (shadow_out = 0).  Hence strength = 0, an
  * all-zero map without sphere casters, and every ray with occ = 0 give pn_draw_colliders' bits.  The maps are read at execution time (a captured
  * launch follows them); the light is a by-value kernel argument, baked into a captured launch like the style.
  * Limits: a collider between two parts of the object is judged against the middle of the column; the object receives no shadow from the colliders; a
- * sphere's own unlit side is not darkened; no penumbra beyond the bilinear footprint and the object's own soft opacity. */
+ * sphere's, box's or capsule's own unlit side is not darkened; no penumbra beyond the bilinear footprint and the object's own soft opacity. */
 typedef struct pn_shadow_light {
     float c[3];            /* the map's centre */
     float L[3];            /* unit vector from the scene towards the light */
@@ -981,7 +1004,7 @@ typedef struct pn_shadow_light {
     int S;                 /* map resolution, 2 .. 4096 */
     float strength;        /* in [0, 1] */
     float bias;            /* world units */
-    int spheres;           /* != 0: solid sphere colliders cast analytic shadows */
+    int spheres;           /* != 0: solid sphere, box and capsule colliders cast analytic shadows */
 } pn_shadow_light;
 /* pn_draw_colliders' arguments and checks, plus: shadow_ws, shadow_depth_0 [S S]; shadow_out [N] or NULL.  PN_ERR_ARG also for S outside 2 .. 4096, a
  * non-finite light entry, half <= 0, strength outside [0, 1], a NULL map, a map overlapping an output, shadow_out overlapping an input or another

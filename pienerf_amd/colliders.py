@@ -15,6 +15,7 @@ from ._lib import ColliderStyle, ShadowLight
 
 SLOTS = 8
 PLANE, SPHERE, CONTAINER = 1, 2, 3
+BOX, CAPSULE = 4, 5
 PLANE_GREY, OTHER_GREY = 0.8, 0.5   # the default colours: a light grey for a plane's slot, a mid grey for every other
 
 
@@ -60,7 +61,7 @@ def shadow_light(direction=(0.4, 1.0, 0.3), strength=0.6, resolution=256, bound=
     """A ShadowLight (pn_shadow_light), built in fp64 and rounded once.  `direction` points from the scene towards the light (any length); the map of
     `resolution`^2 texels is centred on `centre` and spans +-`extent` (None: sqrt(3) `bound`, which covers the box [-bound, bound]^3 from every direction);
     the light rays start half + 2 `min_near` from the centre, so each enters the box beyond min_near; `bias` (None: 1.5 texels) keeps a receiver from
-    shadowing itself; `spheres`: solid sphere colliders cast analytic shadows.  ValueError for a zero or non-finite direction, strength outside [0, 1],
+    shadowing itself; `spheres`: solid sphere, box and capsule colliders cast analytic shadows.  ValueError for a zero or non-finite direction, strength outside [0, 1],
     resolution outside 2 .. 4096, a non-positive extent or a negative bias."""
     d = [float(v) for v in direction]
     c = [float(v) for v in centre]
@@ -110,6 +111,61 @@ def _dot(a, b):
     return a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1] + a[..., 2] * b[..., 2]
 
 
+def _sphere_roots(o, d, q, c, R):
+    oc = o - c
+    b = _dot(oc, d)
+    disc = b * b - q * (_dot(oc, oc) - R * R)
+    sq = torch.sqrt(disc.clamp(min=0))
+    return disc > 0, (-b - sq) / q, (-b + sq) / q
+
+
+def _box_interval(o, d, p, h):
+    """(hit, t_enter, t_exit, face of t_enter, face of t_exit) of the slab test; the lowest axis wins a tie."""
+    inf = float("inf")
+    zero = d == 0
+    dd = torch.where(zero, torch.ones_like(d), d)
+    t1, t2 = ((p - h) - o) / dd, ((p + h) - o) / dd
+    lo = torch.where(zero, torch.full_like(d, -inf), torch.minimum(t1, t2))
+    hi = torch.where(zero, torch.full_like(d, inf), torch.maximum(t1, t2))
+    inside = (~zero | ((o - p).abs() < h)).all(dim=-1)
+    te, fe = lo.max(dim=-1)
+    tx, fx = hi.min(dim=-1)
+    fe = (lo == te.unsqueeze(-1)).to(torch.int64).argmax(dim=-1)   # the first axis that reaches the extremum
+    fx = (hi == tx.unsqueeze(-1)).to(torch.int64).argmax(dim=-1)
+    return inside & (te < tx), te, tx, fe, fx
+
+
+def _capsule_interval(o, d, q, A, n, R):
+    """(hit, t_near, t_far): the convex union of the end spheres and the finite cylinder."""
+    inf = float("inf")
+    length = float(n.norm())
+    ax = n / length
+    okA, nA, fA = _sphere_roots(o, d, q, A, R)
+    okB, nB, fB = _sphere_roots(o, d, q, A + n, R)
+    tn = torch.where(okA, nA, torch.full_like(q, inf))
+    tf = torch.where(okA, fA, torch.full_like(q, -inf))
+    tn = torch.where(okB, torch.minimum(tn, nB), tn)
+    tf = torch.where(okB, torch.maximum(tf, fB), tf)
+    oc = o - A
+    ad, ao = _dot(ax, d), _dot(ax, oc)
+    dp, op = d - ad.unsqueeze(-1) * ax, oc - ao.unsqueeze(-1) * ax
+    A2, b = _dot(dp, dp), _dot(op, dp)
+    disc = b * b - A2 * (_dot(op, op) - R * R)
+    okC = (A2 > 0) & (disc > 0)
+    sq = torch.sqrt(disc.clamp(min=0))
+    A2s = torch.where(A2 > 0, A2, torch.ones_like(A2))
+    lo, hi = (-b - sq) / A2s, (-b + sq) / A2s
+    par = ad == 0
+    ads = torch.where(par, torch.ones_like(ad), ad)
+    s1, s2 = (0 - ao) / ads, (length - ao) / ads
+    lo = torch.where(par, lo, torch.maximum(lo, torch.minimum(s1, s2)))
+    hi = torch.where(par, hi, torch.minimum(hi, torch.maximum(s1, s2)))
+    okC = okC & (~par | ((ao > 0) & (ao < length))) & (lo < hi)
+    tn = torch.where(okC, torch.minimum(tn, lo), tn)
+    tf = torch.where(okC, torch.maximum(tf, hi), tf)
+    return okA | okB | okC, tn, tf
+
+
 @torch.no_grad()
 def draw_colliders_torch(colliders, style, rays_o, rays_d, t_min, t_max, bg, weights_sum, depth_0, image):
     """The law in torch ops, fp32, on the device of the rays: (image, coverage, collider_t), nothing in place.  `colliders`: 8 entries, None or
@@ -120,6 +176,7 @@ def draw_colliders_torch(colliders, style, rays_o, rays_d, t_min, t_max, bg, wei
     q = _dot(d, d)
     t_hit = torch.full_like(s, inf)
     k_hit = torch.full(s.shape, -1, dtype=torch.int64, device=dev)
+    face_hit = torch.zeros_like(k_hit)
     for k, c in enumerate(colliders):
         if c is None:
             continue
@@ -129,6 +186,14 @@ def draw_colliders_torch(colliders, style, rays_o, rays_d, t_min, t_max, bg, wei
             nd = _dot(n, d)
             t = _dot(n, p - o) / nd
             ok = nd < 0
+        elif typ == BOX:
+            ok, te, tx, fe, fx = _box_interval(o, d, p, n)
+            first = te > t_min
+            t = torch.where(first, te, tx)
+            face_hit = torch.where(ok & (t > t_min) & (t < t_max) & (t < t_hit), torch.where(first, fe, fx), face_hit)
+        elif typ == CAPSULE:
+            ok, tn, tf = _capsule_interval(o, d, q, p, n, R)
+            t = torch.where(tn > t_min, tn, tf)
         else:
             oc = o - p
             b = _dot(oc, d)
@@ -166,6 +231,18 @@ def draw_colliders_torch(colliders, style, rays_o, rays_d, t_min, t_max, bg, wei
                 v = torch.linalg.cross(n, u)
                 cells = torch.floor(_dot(u, r) / style.checker) + torch.floor(_dot(v, r) / style.checker)
                 factor = torch.where(torch.remainder(cells, 2) != 0, torch.full_like(t, style.checker_dim), factor)
+        elif typ == BOX:
+            nd = torch.gather(d, 1, face_hit.unsqueeze(-1)).squeeze(-1)
+            if style.checker > 0:
+                ra = torch.where(face_hit == 0, r[..., 1], r[..., 0])
+                rb = torch.where(face_hit == 2, r[..., 1], r[..., 2])
+                cells = torch.floor(ra / style.checker) + torch.floor(rb / style.checker)
+                factor = torch.where(torch.remainder(cells, 2) != 0, torch.full_like(t, style.checker_dim), factor)
+        elif typ == CAPSULE:
+            length = float(n.norm())
+            ax = n / length
+            hc = _dot(ax, r).clamp(0, length)
+            nd = _dot((r - hc.unsqueeze(-1) * ax) / R, d)
         else:
             nd = _dot(r / R, d)
         shade = style.ambient + (1 - style.ambient) * (nd.abs() / dn)

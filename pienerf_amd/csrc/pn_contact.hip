@@ -1,4 +1,4 @@
-// Contact with planes and spheres (include/pienerf_hip.h: pn_contact_state).
+// Contact with planes, spheres, boxes and capsules (include/pienerf_hip.h: pn_contact_state).
 //
 // Ainv is pre-inverted, so contact is an explicit penalty on the right-hand side, scaled by m / dt^2 so that a point's own response to it is at most
 // (kappa + beta) times its penetration.  The force depends on the integration points' current positions and velocities, so — the drag's argument
@@ -174,7 +174,7 @@ __global__ void k_contact_collider(pn_contact_state* __restrict__ st, PnContactS
 }
 
 extern "C" int pn_sim_contact_set_collider(void* state, int index, int type, const double* geom10_host, void* stream) {
-    PN_REQUIRE(state && index >= 0 && index < PN_CONTACT_SLOTS && type >= PN_CONTACT_EMPTY && type <= PN_CONTACT_CONTAINER);
+    PN_REQUIRE(state && index >= 0 && index < PN_CONTACT_SLOTS && type >= PN_CONTACT_EMPTY && type <= PN_CONTACT_CAPSULE);
     PN_REQUIRE(type == PN_CONTACT_EMPTY || geom10_host);
     PnContactSlot s;
     s.index = index; s.type = type;
@@ -184,6 +184,8 @@ extern "C" int pn_sim_contact_set_collider(void* state, int index, int type, con
     }
     if (type == PN_CONTACT_PLANE) PN_REQUIRE(fabs(s.g[3] * s.g[3] + s.g[4] * s.g[4] + s.g[5] * s.g[5] - 1.0) <= 1e-9);  // a unit normal
     if (type == PN_CONTACT_SPHERE || type == PN_CONTACT_CONTAINER) PN_REQUIRE(s.g[6] > 0.0);
+    if (type == PN_CONTACT_BOX) PN_REQUIRE(s.g[3] > 0.0 && s.g[4] > 0.0 && s.g[5] > 0.0 && s.g[6] == 0.0);  // half-extents; R is reserved
+    if (type == PN_CONTACT_CAPSULE) PN_REQUIRE(s.g[3] * s.g[3] + s.g[4] * s.g[4] + s.g[5] * s.g[5] > 0.0 && s.g[6] > 0.0);  // B - A, radius
     k_contact_collider<<<1, 1, 0, (hipStream_t)stream>>>((pn_contact_state*)state, s);
     PN_LAUNCH_CHECK();
     return PN_OK;

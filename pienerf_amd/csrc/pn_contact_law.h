@@ -13,13 +13,31 @@
 __device__ __forceinline__ bool pn_contact_collider_term(const pn_contact_collider* __restrict__ col, double kappa, double beta, double mu, double h, double dt,
                                                          double dt2, const double x[3], const double v[3], double a[3], double* delta_out) {
     const int type = col->type;
-    if (type < PN_CONTACT_PLANE || type > PN_CONTACT_CONTAINER) return false;
+    if (type < PN_CONTACT_PLANE || type > PN_CONTACT_CAPSULE) return false;
     double nh[3], d;
-    const double r0 = x[0] - col->p[0], r1 = x[1] - col->p[1], r2 = x[2] - col->p[2];
+    double r0 = x[0] - col->p[0], r1 = x[1] - col->p[1], r2 = x[2] - col->p[2];
     if (type == PN_CONTACT_PLANE) {
         nh[0] = col->n[0]; nh[1] = col->n[1]; nh[2] = col->n[2];
         d = nh[0] * r0 + nh[1] * r1 + nh[2] * r2;
+    } else if (type == PN_CONTACT_BOX) {  // n: the half-extents
+        const double q0 = fabs(r0) - col->n[0], q1 = fabs(r1) - col->n[1], q2 = fabs(r2) - col->n[2];
+        const double s0 = r0 >= 0.0 ? 1.0 : -1.0, s1 = r1 >= 0.0 ? 1.0 : -1.0, s2 = r2 >= 0.0 ? 1.0 : -1.0;
+        if (fmax(fmax(q0, q1), q2) > 0.0) {  // outside: the Euclidean distance to the face, edge or corner
+            const double e0 = fmax(q0, 0.0), e1 = fmax(q1, 0.0), e2 = fmax(q2, 0.0);
+            d = sqrt(e0 * e0 + e1 * e1 + e2 * e2);
+            nh[0] = s0 * e0 / d; nh[1] = s1 * e1 / d; nh[2] = s2 * e2 / d;
+        } else {  // inside or on the surface: the nearest face, the lowest axis on ties
+            nh[0] = nh[1] = nh[2] = 0.0;
+            if (q0 >= q1 && q0 >= q2) { d = q0; nh[0] = s0; }
+            else if (q1 >= q2) { d = q1; nh[1] = s1; }
+            else { d = q2; nh[2] = s2; }
+        }
     } else {
+        if (type == PN_CONTACT_CAPSULE) {  // n = B - A: the sphere's rule about the segment's closest point c = p + s n
+            const double n0 = col->n[0], n1 = col->n[1], n2 = col->n[2];
+            const double s = fmin(fmax((r0 * n0 + r1 * n1 + r2 * n2) / (n0 * n0 + n1 * n1 + n2 * n2), 0.0), 1.0);
+            r0 = x[0] - (col->p[0] + s * n0); r1 = x[1] - (col->p[1] + s * n1); r2 = x[2] - (col->p[2] + s * n2);
+        }
         const double L = sqrt(r0 * r0 + r1 * r1 + r2 * r2);
         if (L > 0.0) {
             nh[0] = r0 / L; nh[1] = r1 / L; nh[2] = r2 / L;

@@ -4,7 +4,8 @@ deformed point cloud and the per-frame IP state the reference's ``main_render.py
 
     python -m pienerf_amd.main_render --frames 30 --out output_img/chair [--ply model/chair_0.ply] [--ckpt ws/checkpoints/ngp_ep0300.pth]
            [--W 800 --H 800] [--radius 5 --azimuth 0 --elevation 0 --fovy 50] [--force fx fy fz | --drag X0 Y0 X1 Y1] [--pin_shake AX AY AZ HZ] [--pin_twist NX NY NZ DEG HZ [--pin_centre X Y Z]] [--save_ply] [--save_ip_state]
-           [--floor Y] [--collide_sphere CX CY CZ R]... [--collide_inside CX CY CZ R] [--contact_stiffness 0.5 --contact_damping 0.5 --friction 0.5
+           [--floor Y] [--collide_sphere CX CY CZ R]... [--collide_inside CX CY CZ R] [--collide_box CX CY CZ HX HY HZ]...
+           [--collide_capsule AX AY AZ BX BY BZ R]... [--contact_stiffness 0.5 --contact_damping 0.5 --friction 0.5
            --contact_thickness DX/2] [--unpin] [--ball CX CY CZ R MASS [VX VY VZ]]... [--ball_damping C]
            [--wind WX WY WZ [--wind_drag 2] [--gust G HZ] [--gust_wave KX KY KZ]] [--air_drag C] [--vortex PX PY PZ NX NY NZ OMEGA RADIUS]...
            [--blast CX CY CZ STRENGTH RADIUS T0 T1]...
@@ -23,8 +24,10 @@ by its GMLS field before every frame's substep, as OUT/mesh_{f}.ply with the sam
 --pin_shake / --pin_twist move the pinned points of the cloud (Simulator.enable_pin_motion): a sinusoidal translation with amplitude (AX, AY, AZ) at HZ,
 a rotation about the axis (NX, NY, NZ) through --pin_centre (default: the pins' centroid) by DEG sin(2 pi HZ t) degrees; they compose with each other and
 with --force / --drag, and images, --save_ply and --save_mesh follow the moving object.
---floor / --collide_sphere / --collide_inside give the object something to meet (Simulator.enable_contact): a floor at height Y, solid
-spheres (repeatable), a container sphere the object stays inside; --unpin clears every pin of the cloud, so the object can be dropped.  They compose with
+--floor / --collide_sphere / --collide_inside / --collide_box / --collide_capsule give the object something to meet (Simulator.enable_contact;
+DESIGN.md 4.10): a floor at height Y, solid spheres (repeatable), a container sphere the object stays inside, solid axis-aligned boxes with centre
+(CX, CY, CZ) and half-extents (HX, HY, HZ) (repeatable: a table, a step, a ledge), solid capsules of radius R about the segment from (AX, AY, AZ) to
+(BX, BY, BZ) (repeatable: a rod); --unpin clears every pin of the cloud, so the object can be dropped.  They compose with
 --force, --drag, --pin_*, --save_ply and --save_mesh.
 --ball adds a dynamic ball the object pushes back (Simulator.enable_bodies / add_body; repeatable): a solid sphere of radius R and mass
 MASS at (CX, CY, CZ), thrown with (VX, VY, VZ) when given, slowed by --ball_damping per second; it falls under the simulator's gravity, meets the floor
@@ -36,9 +39,9 @@ at --air_drag per second; vortices (repeatable) and blasts with a time window (r
 points closer than --self_thickness (default sim_dx) that were at least --self_exclusion apart at rest (default 3 x the thickness) repel each other.  It
 composes with every other flag.
 --draw_colliders draws those colliders into every frame (SimRenderHarness.draw_colliders): a shaded floor with a checker pattern of
---checker world units (default 2 sim_dx; 0: none) and shaded spheres, depth-tested against the object; --collider_color (repeatable) colours them in slot order
-(the floor first, then the spheres, then the container).  It composes with --bg_radius, --force, --drag, --pin_*, --save_ply and --save_mesh.
---shadows lets the object (and the solid spheres) cast a shadow onto the drawn colliders (SimRenderHarness.cast_shadows): a directional
+--checker world units (default 2 sim_dx; 0: none), shaded spheres and capsules and boxes whose faces carry the checker, depth-tested against the object; --collider_color (repeatable) colours them in slot order
+(the floor first, then the spheres, the container, the boxes, the capsules, then the balls).  It composes with --bg_radius, --force, --drag, --pin_*, --save_ply and --save_mesh.
+--shadows lets the object (and the solid spheres, boxes and capsules) cast a shadow onto the drawn colliders (SimRenderHarness.cast_shadows): a directional
 light from --light (a vector from the scene towards the light, default 0.4 1 0.3), darkening by --shadow_strength at most, through an opacity map of
 --shadow_res texels per side rendered from the light every frame.
 --draw_points paints the simulator's integration points into every frame (SimRenderHarness.draw_points), the reference's "render IPs"
@@ -109,7 +112,8 @@ def bind_rest_mesh(h, args):
 
 
 def wants_contact(args):
-    return args.floor is not None or bool(args.collide_sphere) or args.collide_inside is not None or bool(getattr(args, "ball", None))
+    return (args.floor is not None or bool(args.collide_sphere) or args.collide_inside is not None or bool(getattr(args, "collide_box", None))
+            or bool(getattr(args, "collide_capsule", None)) or bool(getattr(args, "ball", None)))
 
 
 def ball_specs(args):
@@ -130,12 +134,12 @@ def ball_specs(args):
 
 
 def configure_contact(sim, args):
-    """--floor / --collide_sphere / --collide_inside and the contact parameters as calls on `sim`; returns the colliders' indices.  Nothing is called
+    """--floor / --collide_sphere / --collide_inside / --collide_box / --collide_capsule and the contact parameters as calls on `sim`; returns the colliders' indices.  Nothing is called
     without a collider argument."""
     if not wants_contact(args):
         if any(v is not None for v in (args.contact_stiffness, args.contact_damping, args.friction, args.contact_thickness)):
             raise SystemExit("--contact_stiffness / --contact_damping / --friction / --contact_thickness need --floor, --collide_sphere, --collide_inside "
-                             "or --ball")
+                             "or --ball (or --collide_box, --collide_capsule)")
         return []
     d = lambda v, dflt: dflt if v is None else v
     ids = []
@@ -148,8 +152,12 @@ def configure_contact(sim, args):
             ids.append(sim.add_sphere(c[:3], c[3]))
         if args.collide_inside is not None:
             ids.append(sim.add_sphere(args.collide_inside[:3], args.collide_inside[3], inside=True))
+        for c in getattr(args, "collide_box", None) or []:   # behind the older shapes: existing command lines keep their slots
+            ids.append(sim.add_box(c[:3], c[3:6]))
+        for c in getattr(args, "collide_capsule", None) or []:
+            ids.append(sim.add_capsule(c[:3], c[3:6], c[6]))
         balls = ball_specs(args)
-        if balls:   # behind the static colliders: --collider_color's slot order stays floor, spheres, container, then the balls
+        if balls:   # behind the static colliders: --collider_color's slot order stays floor, spheres, container, boxes, capsules, then the balls
             sim.enable_bodies()
             ids.extend(sim.add_body(**b) for b in balls)
     except ValueError as e:   # a parameter out of range, a radius <= 0, a mass <= 0, a ninth collider
@@ -214,7 +222,7 @@ def configure_overlay(h, args):
             raise SystemExit("--collider_color / --checker need --draw_colliders")
         return None
     if not wants_contact(args):
-        raise SystemExit("--draw_colliders needs --floor, --collide_sphere, --collide_inside or --ball")
+        raise SystemExit("--draw_colliders needs --floor, --collide_sphere, --collide_inside or --ball (or --collide_box, --collide_capsule)")
     from .colliders import collider_style
     try:
         style = collider_style(rgb=args.collider_color, types=h.sim.collider_types(), checker=2.0 * args.sim_dx if args.checker is None else args.checker)
@@ -265,7 +273,7 @@ def configure_points(h, args):
 def check_overlay_args(args):
     """What configure_overlay refuses, before anything is built."""
     if args.draw_colliders and not wants_contact(args):
-        raise SystemExit("--draw_colliders needs --floor, --collide_sphere, --collide_inside or --ball")
+        raise SystemExit("--draw_colliders needs --floor, --collide_sphere, --collide_inside or --ball (or --collide_box, --collide_capsule)")
     if not args.draw_colliders and (args.collider_color or args.checker is not None):
         raise SystemExit("--collider_color / --checker need --draw_colliders")
     if args.shadows and not args.draw_colliders:
@@ -509,6 +517,10 @@ def parser():
     ap.add_argument("--collide_sphere", type=float, nargs=4, action="append", default=None, metavar=("CX", "CY", "CZ", "R"),
                     help="a solid sphere the object collides with; repeatable")
     ap.add_argument("--collide_inside", type=float, nargs=4, default=None, metavar=("CX", "CY", "CZ", "R"), help="a container sphere the object stays inside")
+    ap.add_argument("--collide_box", type=float, nargs=6, action="append", default=None, metavar=("CX", "CY", "CZ", "HX", "HY", "HZ"),
+                    help="a solid axis-aligned box with centre (CX, CY, CZ) and half-extents (HX, HY, HZ) the object collides with; repeatable")
+    ap.add_argument("--collide_capsule", type=float, nargs=7, action="append", default=None, metavar=("AX", "AY", "AZ", "BX", "BY", "BZ", "R"),
+                    help="a solid capsule of radius R about the segment from (AX, AY, AZ) to (BX, BY, BZ) the object collides with; repeatable")
     ap.add_argument("--ball", type=float, nargs="+", action="append", default=None, metavar="N",
                     help="CX CY CZ R MASS [VX VY VZ]: a dynamic ball the object pushes back (DESIGN.md 4.17); repeatable")
     ap.add_argument("--ball_damping", type=float, default=None, metavar="C", help="linear damping of every --ball, 1/s, >= 0 (default 0)")
@@ -516,7 +528,7 @@ def parser():
     ap.add_argument("--contact_damping", type=float, default=None, help="share of the approach velocity removed per substep, in [0, 1] (default 0.5)")
     ap.add_argument("--friction", type=float, default=None, help="Coulomb friction coefficient of the colliders, >= 0 (default 0.5)")
     ap.add_argument("--contact_thickness", type=float, default=None, help="contact begins this far outside a collider (default: sim_dx / 2)")
-    ap.add_argument("--unpin", action="store_true", help="clear every pin of the cloud: the object falls (give it a --floor)")
+    ap.add_argument("--unpin", action="store_true", help="clear every pin of the cloud: the object falls (give it a --floor or a --collide_box)")
     ap.add_argument("--wind", type=float, nargs=3, default=None, metavar=("WX", "WY", "WZ"), help="a wind of this velocity blows on the object (force fields, DESIGN.md 4.15)")
     ap.add_argument("--wind_drag", type=float, default=None, metavar="C", help="how hard --wind drags the object along, 1/s, >= 0 (default 2)")
     ap.add_argument("--gust", type=float, nargs=2, default=None, metavar=("G", "HZ"), help="--wind's velocity varies by 1 + G sin(2 pi HZ t), G in [0, 1]")
@@ -532,7 +544,7 @@ def parser():
     ap.add_argument("--self_stiffness", type=float, default=None, metavar="K", help="share of an overlap removed per substep, in (0, 1] (default 0.5)")
     ap.add_argument("--self_damping", type=float, default=None, metavar="B", help="share of the approach velocity removed per substep, in [0, 1] (default 0.5)")
     ap.add_argument("--self_friction", type=float, default=None, metavar="MU", help="friction between the touching parts, >= 0 (default 0)")
-    ap.add_argument("--draw_colliders", action="store_true", help="draw the colliders into every frame (DESIGN.md 4.11); needs --floor, --collide_sphere or --collide_inside")
+    ap.add_argument("--draw_colliders", action="store_true", help="draw the colliders into every frame (DESIGN.md 4.11); needs --floor, --collide_sphere, --collide_inside, --collide_box, --collide_capsule or --ball")
     ap.add_argument("--collider_color", type=float, nargs=3, action="append", default=None, metavar=("R", "G", "B"),
                     help="a collider's colour, in slot order; repeatable (default: a light grey for a plane, a mid grey otherwise)")
     ap.add_argument("--checker", type=float, default=None, metavar="S", help="cell size of the floor's checker pattern (default: 2 sim_dx; 0: none)")

@@ -1,4 +1,4 @@
-"""Contact with planes and spheres (csrc/pn_contact.hip).  A pn_contact_state in device memory, read by two launches in front of every
+"""Contact with planes, spheres, boxes and capsules (csrc/pn_contact.hip).  A pn_contact_state in device memory, read by two launches in front of every
 substep (k_contact_points, k_contact_rhs) that write _rhs_contact = (the chain so far) + the contact term of the state the substep starts from.  The
 parameters and the collider slots are mirrored on the host, so they may be set before initialize() and are uploaded when the state is allocated."""
 import numpy as np
@@ -7,11 +7,13 @@ import torch
 from .._lib import check, lib, ptr, stream_ptr
 from ._stage import Stage, _vec3, torchfloat
 
-__all__ = ["CONTACT_SLOTS", "CONTACT_EMPTY", "CONTACT_PLANE", "CONTACT_SPHERE", "CONTACT_CONTAINER", "CONTACT_COLLIDER_DTYPE", "CONTACT_STATE_DTYPE",
-           "CONTACT_STATE_DOUBLES", "contact_params", "contact_plane", "contact_sphere", "pack_contact_state", "ContactMixin"]   # what solver.py re-exports
+__all__ = ["CONTACT_SLOTS", "CONTACT_EMPTY", "CONTACT_PLANE", "CONTACT_SPHERE", "CONTACT_CONTAINER", "CONTACT_BOX", "CONTACT_CAPSULE",
+           "CONTACT_COLLIDER_DTYPE", "CONTACT_STATE_DTYPE", "CONTACT_STATE_DOUBLES", "contact_params", "contact_plane", "contact_sphere", "contact_box",
+           "contact_capsule", "pack_contact_state", "ContactMixin"]   # what solver.py re-exports
 
 CONTACT_SLOTS = 8          # pn_contact_state's collider slots (include/pienerf_hip.h: PN_CONTACT_SLOTS)
 CONTACT_EMPTY, CONTACT_PLANE, CONTACT_SPHERE, CONTACT_CONTAINER = 0, 1, 2, 3
+CONTACT_BOX, CONTACT_CAPSULE = 4, 5
 # pn_contact_collider / pn_contact_state (include/pienerf_hip.h) as numpy records: 88 and 744 bytes = pn_sim_contact_bytes(), checked in _alloc_contact
 CONTACT_COLLIDER_DTYPE = np.dtype([("type", "<i4"), ("reserved", "<i4"), ("p", "<f8", (3,)), ("n", "<f8", (3,)), ("R", "<f8"), ("v", "<f8", (3,))])
 CONTACT_STATE_DTYPE = np.dtype([("active", "<i4"), ("n", "<i4"), ("kappa", "<f8"), ("beta", "<f8"), ("mu", "<f8"), ("h", "<f8"),
@@ -65,6 +67,35 @@ def contact_sphere(centre, radius, inside=False, velocity=None):
     return (CONTACT_CONTAINER if inside else CONTACT_SPHERE), g
 
 
+def contact_box(centre, half_extents, velocity=None):
+    """(type, geom10) for a solid axis-aligned box: p the centre, n the three half-extents, R = 0 (reserved).  ValueError for a half-extent that is
+    not a finite number > 0."""
+    h = _vec3(half_extents, "a box's half-extents")
+    if not (np.isfinite(h).all() and (h > 0.0).all()):
+        raise ValueError(f"contact: a box's half-extents must be three finite numbers > 0, got {half_extents!r}")
+    g = np.zeros(10)
+    g[0:3], g[3:6] = _vec3(centre, "a box's centre"), h
+    g[7:10] = _vec3(velocity, "a collider's velocity") if velocity is not None else 0.0
+    return CONTACT_BOX, g
+
+
+def contact_capsule(a, b, radius, velocity=None):
+    """(type, geom10) for a solid capsule, the points within `radius` of the segment from `a` to `b`: p = a, n = b - a (not normalised), R = radius.
+    ValueError for a radius that is not > 0 or coinciding end points."""
+    R = float(radius)
+    if not (np.isfinite(R) and R > 0.0):
+        raise ValueError(f"contact: a capsule's radius must be a finite number > 0, got {radius!r}")
+    A = _vec3(a, "a capsule's end point a")
+    n = _vec3(b, "a capsule's end point b") - A
+    nn = float(n[0] * n[0] + n[1] * n[1] + n[2] * n[2])
+    if not (np.isfinite(nn) and nn > 0.0):
+        raise ValueError(f"contact: a capsule's end points must be finite and distinct, got {a!r}, {b!r}")
+    g = np.zeros(10)
+    g[0:3], g[3:6], g[6] = A, n, R
+    g[7:10] = _vec3(velocity, "a collider's velocity") if velocity is not None else 0.0
+    return CONTACT_CAPSULE, g
+
+
 def pack_contact_state(active, params, colliders):
     """The bytes of a pn_contact_state (include/pienerf_hip.h) holding `params` = (kappa, beta, mu, h) and `colliders` = CONTACT_SLOTS entries, each
     None or (type, geom10): what the device state holds after the setters (n = 1 + the highest slot in use)."""
@@ -92,7 +123,7 @@ class ContactMixin:
 
     def enable_contact(self, stiffness=0.5, damping=0.5, friction=0.5, thickness=None):
         """From now on every stepforward() first writes rhs + the contact term (csrc/pn_contact.hip: k_contact_points, k_contact_rhs; include/pienerf_hip.h has the law) and
-        runs the substep with it in the rhs_gravity slot: an explicit penalty against the colliders added with add_plane / add_sphere, evaluated at the
+        runs the substep with it in the rhs_gravity slot: an explicit penalty against the colliders added with add_plane / add_sphere / add_box / add_capsule, evaluated at the
         integration points from the dof / dof_vel that substep starts from; the system matrix and Ainv unchanged.  thickness None: dx / 2 (integration
         points are cell centres, the visible surface lies about half a cell outside them).  The state lives in device memory, so substeps captured into
         graphs after this call follow set_collider / set_contact_params without a recapture.  May be called before initialize(); ValueError for
@@ -159,6 +190,20 @@ class ContactMixin:
         c = contact_sphere(centre, radius, inside, velocity)
         return self._put_collider(self._free_slot(), c)
 
+    def add_box(self, centre, half_extents, velocity=None):
+        """A solid axis-aligned box about `centre` with the three `half_extents` (> 0).  Returns the collider's index; ValueError for a half-extent that
+        is not > 0 or a ninth collider."""
+        self._stage_state(STAGE, gpu=False)
+        c = contact_box(centre, half_extents, velocity)
+        return self._put_collider(self._free_slot(), c)
+
+    def add_capsule(self, a, b, radius, velocity=None):
+        """A solid capsule: everything within `radius` of the segment from `a` to `b`.  Returns the collider's index; ValueError for radius <= 0,
+        a == b or a ninth collider."""
+        self._stage_state(STAGE, gpu=False)
+        c = contact_capsule(a, b, radius, velocity)
+        return self._put_collider(self._free_slot(), c)
+
     def _slot(self, index):
         self._stage_state(STAGE, gpu=False)
         i = int(index)
@@ -166,9 +211,9 @@ class ContactMixin:
             raise ValueError(f"contact: there is no collider {index!r}")
         return i
 
-    def set_collider(self, index, point=None, normal=None, centre=None, radius=None, inside=None, velocity=None):
+    def set_collider(self, index, point=None, normal=None, centre=None, radius=None, inside=None, velocity=None, half_extents=None, a=None, b=None):
         """Changes collider `index` from the next substep on; what is left None keeps its value.  A plane takes point / normal, a sphere centre / radius /
-        inside, both velocity.  A moving collider is scripted from the host with this, per frame, with `velocity` given for the relative velocity.
+        inside, a box centre / half_extents, a capsule a / b / radius, all of them velocity.  A moving collider is scripted from the host with this, per frame, with `velocity` given for the relative velocity.
         ValueError for an index without a collider, an argument of the other kind, a value add_plane / add_sphere would refuse, or a slot that holds
         a dynamic body (bodies.py): the ball moves on the device, so the mirror this call edits is stale — set_body changes it."""
         i = self._slot(index)
@@ -177,11 +222,19 @@ class ContactMixin:
         t, g = self._colliders[i]
         vel = g[7:10] if velocity is None else velocity
         if t == CONTACT_PLANE:
-            if centre is not None or radius is not None or inside is not None:
+            if any(v is not None for v in (centre, radius, inside, half_extents, a, b)):
                 raise ValueError(f"contact: collider {i} is a plane: it takes point, normal and velocity")
             c = contact_plane(g[0:3] if point is None else point, g[3:6] if normal is None else normal, vel)
+        elif t == CONTACT_BOX:
+            if any(v is not None for v in (point, normal, radius, inside, a, b)):
+                raise ValueError(f"contact: collider {i} is a box: it takes centre, half_extents and velocity")
+            c = contact_box(g[0:3] if centre is None else centre, g[3:6] if half_extents is None else half_extents, vel)
+        elif t == CONTACT_CAPSULE:
+            if any(v is not None for v in (point, normal, centre, inside, half_extents)):
+                raise ValueError(f"contact: collider {i} is a capsule: it takes a, b, radius and velocity")
+            c = contact_capsule(g[0:3] if a is None else a, g[0:3] + g[3:6] if b is None else b, g[6] if radius is None else radius, vel)
         else:
-            if point is not None or normal is not None:
+            if point is not None or normal is not None or half_extents is not None or a is not None or b is not None:
                 raise ValueError(f"contact: collider {i} is a sphere: it takes centre, radius, inside and velocity")
             c = contact_sphere(g[0:3] if centre is None else centre, g[6] if radius is None else radius, (t == CONTACT_CONTAINER) if inside is None else inside, vel)
         self._put_collider(i, c)
@@ -216,7 +269,7 @@ class ContactMixin:
         return self._stage_state(STAGE)
 
     def collider_types(self):
-        """The type of every collider slot (CONTACT_EMPTY / _PLANE / _SPHERE / _CONTAINER), from the host mirror."""
+        """The type of every collider slot (CONTACT_EMPTY / _PLANE / _SPHERE / _CONTAINER / _BOX / _CAPSULE), from the host mirror."""
         return [CONTACT_EMPTY if c is None else int(c[0]) for c in self._colliders]
 
     def _enqueue_contact_rhs(self, rhs_in, one_launch=False):

@@ -1,8 +1,8 @@
 #!/usr/bin/env python
 """The collider overlay (csrc/pn_colliders.hip: k_draw_colliders) on the GPU: the launch alone at 800 x 800 with a floor, a solid sphere
-and a container, against the same law restated in torch ops on the device (pienerf_amd.colliders.draw_colliders_torch), and one eager step() of the
+and a container (case `three`), with all eight slots holding boxes (`boxes`) and with all eight holding capsules (`capsules`), against the same law restated in torch ops on the device (pienerf_amd.colliders.draw_colliders_torch), and one eager step() of the
 chair harness with and without the overlay.
-    python tools/time_colliders.py [--W 800 --H 800] [--reps 5000] [--rounds 5] [--steps 200] [--out FILE.json]
+    python tools/time_colliders.py [--W 800 --H 800] [--cases three,boxes,capsules] [--reps 5000] [--rounds 5] [--steps 200] [--out FILE.json]
 HIP events on one stream.  The launch: a graph of 50 launches, replayed, so the figure is the launch's time on a busy stream and not a launch's latency;
 the torch restatement: eager calls (dozens of launches each).  step(): a host clock around `--steps` steps ending in a device synchronise, the two
 harnesses in alternating rounds; medians over the rounds with the rounds' spread.  Before timing, the launch is compared with the torch restatement on
@@ -29,9 +29,16 @@ LAUNCHES = 50
 BYTES_PER_RAY = 12 + 12 + 4 + 4 + 12 + 12 + 4 + 4   # rays_o, rays_d, weights_sum, depth_0, image in and out, coverage, collider_t
 
 
-def colliders():
-    return ([solver.contact_plane((0.0, -0.95, 0.0), (0.0, 1.0, 0.0)), solver.contact_sphere((0.0, 0.0, 0.9), 0.5),
-             solver.contact_sphere((0.0, 0.0, 0.0), 1.6, inside=True)] + [None] * 5)
+def colliders(case="three"):
+    if case == "three":
+        return ([solver.contact_plane((0.0, -0.95, 0.0), (0.0, 1.0, 0.0)), solver.contact_sphere((0.0, 0.0, 0.9), 0.5),
+                 solver.contact_sphere((0.0, 0.0, 0.0), 1.6, inside=True)] + [None] * 5)
+    spots = [(-0.9 + 0.6 * (k % 4), -0.6 + 0.9 * (k // 4), 0.3 - 0.2 * (k % 3)) for k in range(8)]   # two rows of four across the picture
+    if case == "boxes":
+        return [solver.contact_box(c, (0.2, 0.25, 0.15 + 0.02 * k)) for k, c in enumerate(spots)]
+    if case == "capsules":
+        return [solver.contact_capsule((c[0] - 0.15, c[1] - 0.2, c[2]), (c[0] + 0.15, c[1] + 0.2, c[2] + 0.1), 0.12) for c in spots]
+    raise SystemExit(f"time_colliders.py: no case {case!r} (three, boxes, capsules)")
 
 
 def time_events(fn, stream, reps):
@@ -47,7 +54,7 @@ def time_events(fn, stream, reps):
     return e0.elapsed_time(e1) / reps
 
 
-def measure_launch(W, H, reps, rounds):
+def measure_launch(W, H, reps, rounds, case="three"):
     dev = torch.device("cuda:0")
     N = W * H
     pose = torch.from_numpy(scene.orbit_pose(3.3, 5.0, -10.0)).unsqueeze(0).to(dev)
@@ -59,7 +66,7 @@ def measure_launch(W, H, reps, rounds):
     s = torch.where(kind == 0, torch.zeros_like(s), torch.where(kind == 1, torch.ones_like(s), s))
     acc = torch.rand(N, 3, device=dev, generator=g) * s.unsqueeze(-1)
     d0 = s * (2.0 + 2.5 * torch.rand(N, device=dev, generator=g))
-    cols = colliders()
+    cols = colliders(case)
     state = torch.frombuffer(bytearray(solver.pack_contact_state(1, (0.5, 0.5, 0.5, 0.025), cols)), dtype=torch.float64).to(dev)
     style = collider_style(types=[0 if c is None else c[0] for c in cols], checker=0.25)
     image, cov, ct = acc.clone(), torch.empty(N, device=dev), torch.empty(N, device=dev)
@@ -94,9 +101,9 @@ def measure_launch(W, H, reps, rounds):
         hip.append(time_events(graph.replay, st, max(reps // LAUNCHES, 4)) * 1e3 / LAUNCHES)
         ops.append(time_events(restated, st, max(reps // 10, 4)) * 1e3)
     med = statistics.median
-    res = dict(W=W, H=H, rays=N, launch_us=med(hip), launch_us_rounds=hip, torch_restatement_us=med(ops), torch_restatement_us_rounds=ops,
+    res = dict(case=case, W=W, H=H, rays=N, launch_us=med(hip), launch_us_rounds=hip, torch_restatement_us=med(ops), torch_restatement_us_rounds=ops,
                bytes_per_ray=BYTES_PER_RAY, launch_GB_per_s=N * BYTES_PER_RAY / (med(hip) * 1e-6) / 1e9, agreement=agree)
-    print(f"launch at {W} x {H} ({N} rays, floor + sphere + container): {res['launch_us']:.2f} us ({min(hip):.2f}..{max(hip):.2f}), "
+    print(f"launch at {W} x {H} ({N} rays, {'floor + sphere + container' if case == 'three' else 'eight ' + case}): {res['launch_us']:.2f} us ({min(hip):.2f}..{max(hip):.2f}), "
           f"{res['launch_GB_per_s']:.0f} GB/s of the {BYTES_PER_RAY} B per ray it has to move; torch restatement {res['torch_restatement_us']:.1f} us "
           f"({min(ops):.1f}..{max(ops):.1f}); agreement {agree}", flush=True)
     return res
@@ -139,6 +146,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--W", type=int, default=800)
     ap.add_argument("--H", type=int, default=800)
+    ap.add_argument("--cases", default="three,boxes,capsules")
     ap.add_argument("--reps", type=int, default=5000)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--steps", type=int, default=200)
@@ -146,7 +154,8 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("time_colliders.py measures on a GPU; none is visible")
-    out = dict(launch=measure_launch(args.W, args.H, args.reps, args.rounds), step=measure_step(args.W, args.H, args.steps, args.rounds))
+    launches = [measure_launch(args.W, args.H, args.reps, args.rounds, case) for case in args.cases.split(",")]
+    out = dict(launch=launches[0], launches=launches, step=measure_step(args.W, args.H, args.steps, args.rounds))
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
