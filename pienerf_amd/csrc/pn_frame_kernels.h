@@ -485,7 +485,7 @@ __global__ void __launch_bounds__(256) k_frame_prologue(FramePrologue a) {
         if (ip < a.n_vtx) a.rec[t] = pnm2::pack_ip_float(j, ip, a.p_ori, a.p_def, a.F_IP, a.dF_IP);
         return;
     }
-    if (b < a.list_blocks + a.pack_blocks + a.gr_blocks) {  // region map of the density bitfield (pn_march_window.h: region_dda)
+    if (b < a.list_blocks + a.pack_blocks + a.gr_blocks) {  // region map of the density bitfield (pn_march_skip.h: region_dda)
         const int R = a.gr_R, n_reg = R * R * R;
         const int r = threadIdx.x + (b - a.list_blocks - a.pack_blocks) * 256;
         if (r < n_reg) {

@@ -2,10 +2,11 @@
 // Part of the render unit (included by pn_render_ops.hip only).
 #pragma once
 #include "pn_march_static.h"
+#include "pn_march_skip.h"
 #include "pn_march_window.h"
 #include "pn_render_records.h"
 
-// One lane per ray slot: fast-forward over the leading run of IP-free search cells.
+// One lane per ray slot: fast-forward over the leading run of IP-free search cells (pn_march_skip.h).
 __global__ void __launch_bounds__(256) k_march_skip(pnm::MarchParams a, pnm2::March2Tables tb, MarchIO io) {
     extern __shared__ uint32_t bits_lds[];
     uint32_t n_alive = io.n_alive;
@@ -34,21 +35,19 @@ __global__ void __launch_bounds__(256) k_march_skip(pnm::MarchParams a, pnm2::Ma
     if (n < n_alive) {
         unsigned n_iter = 0;
         const int index = io.rays_alive[n];
-        float far = a.fars[index];
-        if (cell_bits2) {  // shorten the ray to where it can still find candidates
+        pnm3::RayConsts c;
+        pnm3::ray_consts(a, index, c);
+        if (cell_bits2) {  // shorten the ray to where it can still find candidates (the end is taken as it comes: near >= the driver's min_near > 0)
             const float near = a.rays_t[index];
-            if (near < far) {
-                const pnm3::Float3 o = *reinterpret_cast<const pnm3::Float3*>(a.rays_o + (size_t)index * 3),
-                                   d = *reinterpret_cast<const pnm3::Float3*>(a.rays_d + (size_t)index * 3);
-                far = pnm3::ray_end_of_candidates(a, cell_bits2, o.x, o.y, o.z, d.x, d.y, d.z, near, far);
-            }
-            io.fars_eff[index] = far;
+            if (near < c.far) c.far = pnm3::ray_end_of_candidates(a, c, cell_bits2, near);
+            io.fars_eff[index] = c.far;
         }
-        const float t = pnm3::skip_empty_cells(a, tb, index, io.noises ? io.noises[n] : 0.0f, &n_iter, cell_bits, cell_bits2 ? far : -1.0f,
-                                               io.dda_start ? cell_bits2 : nullptr, io.dda_start && cell_bits2 ? io.hop_budget : 0, grid_regions, io.grid_regions_R);
+        const bool dda = io.dda_start && cell_bits2;
+        const pnm3::SkipMaps maps{cell_bits, dda ? cell_bits2 : nullptr, grid_regions, io.grid_regions_R, dda ? io.hop_budget : 0};
+        const float t = pnm3::skip_empty_cells(a, tb, c, maps, index, io.noises ? io.noises[n] : 0.0f, &n_iter);
         io.t_resume[n] = t;
         if (!PN_DBG_PHASES_ON && a.stats && n_iter) atomicAdd(a.stats, (unsigned long long)n_iter);
-        work = t < far;
+        work = t < c.far;
         if (io.active && !work) {  // nothing left to march: k_march will not visit the slot, so its (single, n_step == 1) sample slot is ended here
             const uint32_t n_step = (uint32_t)io.trip->n_step;
             float* dl = io.deltas + (size_t)n * n_step * 2;

@@ -1,5 +1,5 @@
 // Side tables and per-point helpers of the ray march (gfx950): the candidate lists, the packed IP records, the Newton inverse
-// warp through one record.  The march itself (windows, skip pre-pass) is in pn_march_window.h.
+// warp through one record.  The march itself is in pn_march_window.h (windows) and pn_march_skip.h (skip pre-pass), over pn_march_seq.h.
 //
 // Per-frame side tables (built by k_frame_prologue in pn_frame_kernels.h / k_nb_* + k_pack_ip in pn_side_tables.h):
 //   nb_rng[n_grid], nb[...]    per cell (begin, end) of: the candidates of its 27-cell neighbourhood as float4(p_def.xyz, bitcast id), in the

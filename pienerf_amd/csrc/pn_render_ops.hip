@@ -4,7 +4,7 @@
 //   pn_render_records.h   records shared by the trip kernels and the driver (PnTrip, PnGroup, PnFrameDev, MarchIO, MarchSide, PN_SEGS, TailEntry)
 //   pn_cell_hash.h        spatial hash of the integration points and its scans
 //   pn_side_tables.h      op-level build of the march's side tables
-//   pn_march_kernels.h    k_march_skip, k_march, k_march_tail, k_march_static_trip (pn_march_window.h, pn_march_static.h)
+//   pn_march_kernels.h    k_march_skip, k_march, k_march_tail, k_march_static_trip (pn_march_skip.h and pn_march_window.h over pn_march_seq.h; pn_march_static.h)
 //   pn_composite.h        composite_one, k_composite
 //   pn_compact.h          k_compact, trip_epilogue, k_composite_compact, k_list_pack
 //   pn_frame_kernels.h    pn_frame, k_frame_tables, k_frame_prologue, k_frame_finish (behind pn_trips_fused.h: the fused trip launch)
@@ -275,7 +275,7 @@ static FramePlan make_frame_plan(const pn_frame* f, const pn_render_opts* o, uin
     // care of frames with more) instead of 8192 mostly empty workgroups per launch — what an empty captured trip costs is dispatch
     p.march_grid_later = std::max(std::min(pn_div_up(N, 256), p.march_grid), (uint32_t)PN_SEGS);
     p.tail_grid = std::max(std::min(pn_div_up(N, 4), 1024u), (uint32_t)PN_SEGS / 4);  // x4 waves, one unfinished ray per wave at a time; every tail segment needs a wave
-    // k_march_skip: DDA start + hop budget (pn_march_window.h: skip_empty_cells); pn_march_set_skip_dda(0) walks hop by hop like rounds 1-2 (same results bit for bit)
+    // k_march_skip: DDA start + hop budget (pn_march_skip.h: skip_empty_cells); pn_march_set_skip_dda(0) walks hop by hop like rounds 1-2 (same results bit for bit)
     p.dda_start = g_skip_dda_override >= 0 ? g_skip_dda_override : 1;
     p.skip_hop_budget = 8;
     // a frame's first trip with ONE lane per ray in pass 1 (k_march<.., 1>) for this many rounds = visited points before a ray goes to the windows
@@ -285,7 +285,7 @@ static FramePlan make_frame_plan(const pn_frame* f, const pn_render_opts* o, uin
     p.bit_words = (f->max_cells + 31) / 32;
     p.short_rays = !is_static && !o->cut && p.bit_words * 8 <= 48 * 1024;  // both maps in LDS: rays end where their candidates end
     p.skip_bits_words = (p.short_rays || p.bit_words * 4 <= 48 * 1024) ? (int)p.bit_words : 0;
-    // --cut: the region map for the skip pre-pass (MarchIO::grid_regions; pn_march_window.h: region_dda) where its assumptions hold: the top cascade level
+    // --cut: the region map for the skip pre-pass (MarchIO::grid_regions; pn_march_skip.h: region_dda) where its assumptions hold: the top cascade level
     // spans exactly +-bound (bound == 2^(C - 1)), regions are whole 64-byte lines of the bitfield and nest on every level, the map fits.
     // Regions of 8^3 voxels (a 64-byte line of the bitfield); 4^3-voxel regions measured 232 against 177 us on the trex option set (hop by hop 285)
     p.reg_R = o->grid_size / 8;
@@ -293,7 +293,7 @@ static FramePlan make_frame_plan(const pn_frame* f, const pn_render_opts* o, uin
                         o->bound == (float)(1u << (o->cascade - 1)) && (p.reg_R / 2) % (1u << (o->cascade - 1)) == 0 &&
                         (uint64_t)p.reg_R * p.reg_R * p.reg_R / 32 * o->cascade <= PN_GRID_REGION_WORDS && ((uintptr_t)bitfield & 15) == 0;
     p.grid_region_words_1 = reg_ok ? (int)((uint64_t)p.reg_R * p.reg_R * p.reg_R / 32) : 0;  // one map
-    p.grid_region_words = p.grid_region_words_1 * (int)o->cascade;                            // one per minimum mip level (pn_march_window.h)
+    p.grid_region_words = p.grid_region_words_1 * (int)o->cascade;                            // one per minimum mip level (pn_march_skip.h)
     p.skip_lds = (size_t)p.skip_bits_words * 4 * (p.short_rays ? 2 : 1) + (size_t)p.grid_region_words * 4;
     // ray groups (ray_batch > 0): per-batch trip schedules inside the same launches
     p.group_rays = o->ray_batch > 0 ? (uint32_t)o->ray_batch : 0u;

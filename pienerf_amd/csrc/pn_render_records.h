@@ -98,7 +98,7 @@ struct MarchIO {
     // frame-driver mode (trip != nullptr): counts come from device memory, valid sample slots are appended to `list`
     PnTrip* trip;
     int* list;
-    float* t_resume;  // optional [n_alive]: written by k_march_skip, read by k_march (pn_march_tables.h: skip_empty_cells)
+    float* t_resume;  // optional [n_alive]: written by k_march_skip, read by k_march (pn_march_skip.h: skip_empty_cells)
     // optional tail pass: rays unfinished after `max_rounds` windows in k_march are appended here (counters zeroed by the caller)
     struct TailEntry* tail;
     int* tail_counts;   // segmented (see PN_SEGS): rays with a long way to go, appended from the front of the segment's region
@@ -122,15 +122,15 @@ struct MarchIO {
     const uint32_t* cell_bits;
     int cell_bits_words;
     // optional (with cell_bits): the cells within one cell of a cell with candidates, and where k_march_skip writes each ray's shortened end
-    // (pn_march_window.h: ray_end_of_candidates); the march kernels then run with MarchParams::fars = fars_eff
+    // (pn_march_skip.h: ray_end_of_candidates); the march kernels then run with MarchParams::fars = fars_eff
     const uint32_t* cell_bits2;
     float* fars_eff;
     // optional (frame driver with ray groups, see PnGroup): this trip's group records
     const PnGroup* groups;
     uint32_t group_rays;
     int lane_per_ray;           // k_march: one lane per ray instead of eight (the throughput form of a frame's first trip)
-    int dda_start, hop_budget;  // k_march_skip: restart the hop chain just before the first cell with candidates; hops before a ray is handed on (pn_march_window.h)
-    // optional (--cut frames): the region map of pn_march_window.h (region_dda) — one bit per 8^3-voxel block of the top cascade level, set when a point of
+    int dda_start, hop_budget;  // k_march_skip: restart the hop chain just before the first cell with candidates; hops before a ray is handed on (pn_march_skip.h)
+    // optional (--cut frames): the region map of pn_march_skip.h (region_dda) — one bit per 8^3-voxel block of the top cascade level, set when a point of
     // the region can meet an occupied voxel on any level or the cut box (k_frame_prologue); k_march_skip keeps it in LDS
     const uint32_t* grid_regions;
     int grid_regions_words;

@@ -205,7 +205,7 @@ def skip_dda():
 
 @pytest.mark.parametrize("radius,theta,phi", [(5.0, 20.0, -15.0), (2.2, 75.0, -40.0), (9.0, -60.0, 5.0), (5.0, 0.0, 0.0), (5.0, 90.0, 0.0)])
 def test_frame_independent_of_the_skip_pre_pass_form(deformed_ip_state, small_opt, ckpt, skip_dda, radius, theta, phi):
-    """Trip 0's skip pre-pass with the DDA start + hop budget (pn_march_window.h: skip_empty_cells; the default) and walking hop by hop (rounds 1-2): the same
+    """Trip 0's skip pre-pass with the DDA start + hop budget (pn_march_skip.h: skip_empty_cells; the default) and walking hop by hop (rounds 1-2): the same
     samples (count, trips) and the same pixels bit for bit, from far, from close (rays crossing a binade of t), and along the grid axes (rays nearly
     parallel to cell faces: the cases the DDA refuses or hands on)."""
     W = 96
@@ -235,7 +235,7 @@ def test_frame_independent_of_the_skip_pre_pass_form(deformed_ip_state, small_op
     (4.0, 1.0 / 256, 0.05, 2.5, -120.0, -5.0),
 ])
 def test_cut_frame_independent_of_the_region_skip(deformed_ip_state, small_opt, skip_dda, bound, dt_gamma, blob_frac, radius, theta, phi):
-    """--cut frames with the skip pre-pass crossing the static background's empty regions on the ray's t-sequence (pn_march_window.h: region_dda; the default)
+    """--cut frames with the skip pre-pass crossing the static background's empty regions on the ray's t-sequence (pn_march_skip.h: region_dda; the default)
     and visiting them voxel by voxel (pn_march_set_skip_dda(0)): the same trips, the same sample count and the same pixels bit for bit — over one, two and three
     cascades, fixed and growing steps, sparse and dense backgrounds (random 8^3-voxel blocks of the bitfield on every level), a camera inside the volume and
     rays along the grid axes."""

@@ -159,7 +159,7 @@ def test_strided_subset_of_the_full_frame_matches_the_oracle(full):
 def test_full_trex_frame_independent_of_the_skip_pre_pass_form():
     """BASELINE configs[2] as bench.py builds it (1008 x 756, bound 2 with two cascades, --cut, dt_gamma 1 / 128, static background in 2 % of the density
     blocks, deformed by 12 substeps under the bench's force): the frame with the skip pre-pass crossing the static background's empty regions on the
-    ray's t-sequence (pn_march_window.h: region_dda, the default) and visiting them voxel by voxel (pn_march_set_skip_dda(0)) — the same trip records,
+    ray's t-sequence (pn_march_skip.h: region_dda, the default) and visiting them voxel by voxel (pn_march_set_skip_dda(0)) — the same trip records,
     the same number of marched samples, the same pixels bit for bit; from three camera poses (rays along different axes, grazing the volume's faces)."""
     from pienerf_amd._lib import check, lib
     from pienerf_amd.harness import SimRenderHarness
