@@ -704,6 +704,61 @@ int pn_sim_contact_rhs(int n_k, int n_IP, const void* state, double dt, double d
 int pn_sim_accel_rhs(int n_k, int n_IP, double dx, const double* rho, const int* kernel_bg, const int* kernel_cnt, const int* buffer,
                      const double* Nx_csr, const double* accel, const double* rhs_in, double* rhs_out, void* stream);
 
+/* Mesh colliders: signed-distance grids (csrc/pn_sdf.hip; pienerf_amd/sdf.py: SdfGrid; Simulator.add_mesh_collider).
+ *
+ * A grid holds fp32 values phi [nz, ny, nx] in device memory; node (i, j, k), i along x, is at lo + s (i, j, k) with cubic voxels of spacing s > 0;
+ * 2 .. 512 nodes per axis, at most 2^27 nodes; lo and s are fp64.
+ *
+ * pn_sdf_build fills a grid from a triangle mesh in ONE launch.  tri9 [T, 9] fp32: the three corners of every triangle, gathered by the host, which
+ * has dropped the triangles with a repeated index or zero area.  For node q = fp32(lo + s (i, j, k)) (the sum in fp64, rounded once per axis), over
+ * the triangles 0 .. T-1 in ascending order, with a, b, c the corners minus q, all terms fp32:
+ *     distance: the squared length of the point of the triangle closest to the origin, by the face / edge / vertex regions (in the order vertex a,
+ *         vertex b, edge ab, vertex c, edge ac, edge bc, face; barycentric products d1 .. d6 as in Ericson, Real-Time Collision Detection 5.1.5);
+ *         the minimum is kept squared and its square root is taken once at the end;
+ *     sign: the generalised winding number w = (1 / 4 pi) sum_t 2 atan2(a.(b x c), |a||b||c| + (a.b)|c| + (b.c)|a| + (c.a)|b|): the terms fp32,
+ *         the sum fp64.  The node is inside iff |w| >= 0.5, and its value is then -dist: either orientation of a closed mesh works.
+ * winding_out (NULL, or [nz, ny, nx] fp64) receives w.  The host wrapper (SdfGrid.from_mesh) derives from it closedness = max | |w| - round(|w|) |
+ * over the nodes off the surface (value beyond 1e-5 s; a node on a face sees w = 1/2) and warns above 0.1: an open mesh has no inside.  One thread per node, 256-thread workgroups over bricks of 8 x 8 x 4 nodes, the triangles
+ * staged through LDS in tiles of 128 that every lane reads at the same address; no atomics, so two builds are the same bits.  The cost is
+ * nodes x triangles; there is no acceleration structure, so the one launch is capped at PN_SDF_MAX_PAIRS = 2^38 node-triangle pairs.  PN_ERR_ARG,
+ * before anything is enqueued, for a NULL pointer, T outside 1 .. 2^24, a node count out of range, more pairs than the cap, lo or s not finite, s <= 0.  No allocation, no host synchronisation. */
+#define PN_SDF_MAX_PAIRS (1ull << 38)
+int pn_sdf_build(const float* tri9, int n_tris, int nx, int ny, int nz, const double* lo3_host, double spacing, float* grid, double* winding_out,
+                 void* stream);
+/* Contact against up to 4 placed grids: a second, optional state of the contact stage.  At integration point i (x_i, v_i as above, fp64), for the
+ * slots 0 .. 3 in index order, a slot with grid != NULL:
+ *     u = (x - lo) / s per axis; a point with u outside [0, n - 1) on any axis, or not finite, gets nothing from the slot;  i0 = floor(u), f = u - i0;
+ *     d = the trilinear interpolant of the eight values about the point (each widened to fp64), lerp(a, b, f) = a + f (b - a) along x, then y, then z;
+ *     g = the gradient of that interpolant in u (g_x = the y-then-z lerp of the four differences along x; g_y = the z lerp of the difference of the
+ *         two y neighbours after the x lerp; g_z = the difference of the two z neighbours after the x and y lerps), nh = g / |g|, (0, 1, 0) for g = 0;
+ *     then contact's own response with its kappa, beta, mu, h and the slot's velocity v: delta = max(h - d, 0), a_n, a_t and a_i += ... as above.
+ * The slot's lo is the grid's lo plus the collider's offset: a placed grid is translated, never rotated or scaled. */
+#define PN_SDF_SLOTS 4
+typedef struct pn_sdf_slot {   /* 80 bytes */
+    const float* grid;   /* device memory, [nz, ny, nx]; NULL: the slot is empty */
+    int nx, ny, nz;      /* nodes per axis, 2 .. 512 */
+    int reserved;
+    double lo[3];        /* position of node (0, 0, 0) */
+    double s;            /* spacing, > 0 */
+    double v[3];         /* the collider's velocity */
+} pn_sdf_slot;
+typedef struct pn_sdf_state {  /* 328 bytes = 41 doubles */
+    int n;               /* 1 + the highest slot in use (<= 4); 0: nothing is added */
+    int reserved;
+    pn_sdf_slot c[PN_SDF_SLOTS];
+} pn_sdf_state;
+uint64_t pn_sim_sdf_bytes(void);         /* sizeof(pn_sdf_state) = 328 */
+/* Writes slot `index` (0 .. 3) and recomputes n.  grid NULL clears the slot (the other arguments are then ignored); else nx, ny, nz in 2 .. 512 with
+ * at most 2^27 nodes and geom7_host = (lo[3], s, v[3]) finite with s > 0, else PN_ERR_ARG.  A one-thread launch on `stream`. */
+int pn_sim_sdf_set_collider(void* state, int index, const float* grid, int nx, int ny, int nz, const double* geom7_host, void* stream);
+/* pn_sim_contact_rhs's two-launch form with the grids between its launches, THREE launches: the analytic law at every point into accel_out
+ * (k_contact_points, as pn_sim_contact_rhs enqueues it); a thread per point adds the grids' terms to accel_out[i] (a point no grid touches keeps
+ * its bits; nothing is added while the contact state is inactive); the per-kernel sum of pn_sim_accel_rhs.  With an empty sdf_state rhs_out and
+ * accel_out are pn_sim_contact_rhs's to the bit.  accel_out is required.  No atomics, no allocation, no host synchronisation, capturable. */
+int pn_sim_contact_sdf_rhs(int n_k, int n_IP, const void* state, const void* sdf_state, double dt, double dx, const double* dof, const double* dof_vel,
+                           const int* topo, const double* rho, const double* Nx, const int* kernel_bg, const int* kernel_cnt, const int* buffer,
+                           const double* Nx_csr, const double* rhs_in, double* rhs_out, double* accel_out, void* stream);
+
 /* Rigid balls (csrc/pn_bodies.hip; Simulator.enable_bodies / add_body): up to 8 dynamic spheres the object pushes back.  A dynamic
  * body b is bound to slot b of a pn_contact_state that holds a solid sphere (PN_CONTACT_SPHERE, radius R); it has a mass M > 0 and a linear damping
  * c >= 0 (1/s).  Its centre p and velocity u ARE the slot's p and v: there is no second copy, so contact, the drawn frame and the shadows follow a

@@ -10,6 +10,8 @@ STAGE_NOT_CAPTURED = {
     "bodies": "bodies: {what} was captured before enable_bodies(), its substep does not move the balls: {again} again",
     "fields": "fields: {what} was captured before enable_fields(), its substep ignores the force fields: {again} again",
     "self": "self-contact: {what} was captured before enable_self_contact(), its substep ignores self-contact: {again} again",
+    # not one of Simulator.STAGES: the contact stage's second state, reported by enabled_stage_names() while a mesh collider exists
+    "mesh_colliders": "mesh colliders: {what} was captured before add_mesh_collider(), its substep ignores the mesh colliders: {again} again",
 }
 # kind of capture: (what the network-form error calls it, what the others call it, the call that captures it again)
 _WORDS = {"graph": ("the step", "the step graph", "capture()"), "pipe": ("the pipeline", "the pipeline", "capture_pipelined()")}

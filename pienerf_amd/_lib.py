@@ -149,6 +149,10 @@ SIGNATURES = {
     "pn_sim_contact_set_collider": (i32, [P, i32, i32, P, P]),
     "pn_sim_contact_rhs": (i32, [i32, i32, P, f64, f64, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "pn_sim_accel_rhs": (i32, [i32, i32, f64, P, P, P, P, P, P, P, P, P]),
+    "pn_sdf_build": (i32, [P, i32, i32, i32, i32, P, f64, P, P, P]),
+    "pn_sim_sdf_bytes": (u64, []),
+    "pn_sim_sdf_set_collider": (i32, [P, i32, P, i32, i32, i32, P, P]),
+    "pn_sim_contact_sdf_rhs": (i32, [i32, i32, P, P, f64, f64, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "pn_sim_bodies_bytes": (u64, []),
     "pn_sim_bodies_work_bytes": (u64, [i32]),
     "pn_sim_bodies_set_params": (i32, [P, i32, P, P]),

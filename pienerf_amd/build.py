@@ -54,6 +54,9 @@ UNITS = {
     # the rigid balls: the per-collider law (pn_contact_law.h) and a point's state (pn_sim_rhs.h) are contact's own lines, contracted alike, so slot
     # b's term at a point is the same bits on the object's side and in the ball's reaction
     "pn_bodies.hip": ["-ffp-contract=fast"],
+    # mesh colliders: the grids' contact term is contact's own response (pn_contact_law.h) at pn_sim_rhs.h's point state, contracted as in the units
+    # it shares them with; the builder's fp32 distances and winding terms are compared with tests/sdf_reference.py's fp64 by a measured bar
+    "pn_sdf.hip": ["-ffp-contract=fast"],
     # the one decision self-contact takes in floating point (a pair's eligibility at rest) switches contraction off for itself
     "pn_selfcontact.hip": ["-ffp-contract=fast"],
     # the diagnostics readout: pn_sim_rhs.h's point state and pn_sim_svd.h's ip_F_partial / svd3, contracted as in the units it shares them with;

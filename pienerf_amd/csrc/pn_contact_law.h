@@ -50,10 +50,32 @@ __device__ __forceinline__ bool pn_contact_collider_term(const pn_contact_collid
             nh[0] = -nh[0]; nh[1] = -nh[1]; nh[2] = -nh[2];
         }
     }
+    // from here on the lines are restated in pn_contact_response below (the signed-distance grids): a change to either goes into both
     const double delta = h - d;
     if (!(delta > 0.0)) return false;
     *delta_out = delta;
     const double w0 = v[0] - col->v[0], w1 = v[1] - col->v[1], w2 = v[2] - col->v[2];
+    const double wn = w0 * nh[0] + w1 * nh[1] + w2 * nh[2];
+    const double t0 = w0 - wn * nh[0], t1 = w1 - wn * nh[1], t2 = w2 - wn * nh[2];
+    const double an = (kappa * delta + beta * fmin(fmax(-wn, 0.0) * dt, delta)) / dt2;
+    a[0] += an * nh[0]; a[1] += an * nh[1]; a[2] += an * nh[2];
+    const double wt = sqrt(t0 * t0 + t1 * t1 + t2 * t2);
+    if (wt > 0.0) {
+        const double at = fmin(mu * an, wt / dt), s = at / wt;
+        a[0] -= s * t0; a[1] -= s * t1; a[2] -= s * t2;
+    }
+    return true;
+}
+
+// The same response for a solid given by a signed distance d and a unit normal nh alone (the signed-distance grids of pn_sdf.hip), moving with
+// velocity cv: the lines of pn_contact_collider_term from `delta` on, restated here rather than shared with it so that the analytic colliders' code,
+// and with it their bits, stay what they were.  delta = 0 adds exactly nothing and leaves *delta_out alone.
+__device__ __forceinline__ bool pn_contact_response(const double nh[3], double d, const double cv[3], double kappa, double beta, double mu, double h, double dt,
+                                                    double dt2, const double v[3], double a[3], double* delta_out) {
+    const double delta = h - d;
+    if (!(delta > 0.0)) return false;
+    *delta_out = delta;
+    const double w0 = v[0] - cv[0], w1 = v[1] - cv[1], w2 = v[2] - cv[2];
     const double wn = w0 * nh[0] + w1 * nh[1] + w2 * nh[2];
     const double t0 = w0 - wn * nh[0], t1 = w1 - wn * nh[1], t2 = w2 - wn * nh[2];
     const double an = (kappa * delta + beta * fmin(fmax(-wn, 0.0) * dt, delta)) / dt2;

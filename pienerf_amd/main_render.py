@@ -7,6 +7,7 @@ deformed point cloud and the per-frame IP state the reference's ``main_render.py
            [--floor Y] [--collide_sphere CX CY CZ R]... [--collide_inside CX CY CZ R] [--collide_box CX CY CZ HX HY HZ]...
            [--collide_capsule AX AY AZ BX BY BZ R]... [--contact_stiffness 0.5 --contact_damping 0.5 --friction 0.5
            --contact_thickness DX/2] [--unpin] [--ball CX CY CZ R MASS [VX VY VZ]]... [--ball_damping C]
+           [--collide_mesh PLY [DX DY DZ]]... [--mesh_collider_res 64]
            [--wind WX WY WZ [--wind_drag 2] [--gust G HZ] [--gust_wave KX KY KZ]] [--air_drag C] [--vortex PX PY PZ NX NY NZ OMEGA RADIUS]...
            [--blast CX CY CZ STRENGTH RADIUS T0 T1]...
            [--self_contact [--self_thickness H] [--self_exclusion R] [--self_stiffness 0.5] [--self_damping 0.5] [--self_friction 0]]
@@ -29,6 +30,9 @@ DESIGN.md 4.10): a floor at height Y, solid spheres (repeatable), a container sp
 (CX, CY, CZ) and half-extents (HX, HY, HZ) (repeatable: a table, a step, a ledge), solid capsules of radius R about the segment from (AX, AY, AZ) to
 (BX, BY, BZ) (repeatable: a rod); --unpin clears every pin of the cloud, so the object can be dropped.  They compose with
 --force, --drag, --pin_*, --save_ply and --save_mesh.
+--collide_mesh gives it an arbitrary static shape (Simulator.add_mesh_collider; repeatable, at most 4): the closed triangle mesh in
+PLY (--save_mesh's file, or python -m pienerf_amd.sdf --terrain), moved by (DX, DY, DZ), becomes a signed-distance grid with --mesh_collider_res nodes
+along its longest axis, built on the device in nodes x triangles work.  It enables contact by itself; the balls ignore it and it is not drawn.
 --ball adds a dynamic ball the object pushes back (Simulator.enable_bodies / add_body; repeatable): a solid sphere of radius R and mass
 MASS at (CX, CY, CZ), thrown with (VX, VY, VZ) when given, slowed by --ball_damping per second; it falls under the simulator's gravity, meets the floor
 and the other colliders, and --draw_colliders / --shadows draw it where it is.  It enables contact by itself and composes with every other flag.
@@ -111,9 +115,61 @@ def bind_rest_mesh(h, args):
     return binding, triangles, colors
 
 
-def wants_contact(args):
+def wants_analytic_collider(args):
     return (args.floor is not None or bool(args.collide_sphere) or args.collide_inside is not None or bool(getattr(args, "collide_box", None))
             or bool(getattr(args, "collide_capsule", None)) or bool(getattr(args, "ball", None)))
+
+
+def wants_contact(args):
+    return wants_analytic_collider(args) or bool(getattr(args, "collide_mesh", None))
+
+
+def mesh_collider_specs(args):
+    """--collide_mesh / --mesh_collider_res as a list of (path, offset); SystemExit for a --collide_mesh that has not 1 or 4 values, a fifth one, an
+    offset that is no number, a resolution out of range or --mesh_collider_res without --collide_mesh."""
+    specs = getattr(args, "collide_mesh", None) or []
+    res = getattr(args, "mesh_collider_res", None)
+    if not specs:
+        if res is not None:
+            raise SystemExit("--mesh_collider_res needs --collide_mesh")
+        return []
+    if len(specs) > 4:
+        raise SystemExit(f"--collide_mesh: at most 4 mesh colliders, got {len(specs)}")
+    if res is not None and not 6 <= res <= 512:
+        raise SystemExit(f"--mesh_collider_res: 6 .. 512 nodes along the longest axis, got {res}")
+    out = []
+    for m in specs:
+        if len(m) not in (1, 4):
+            raise SystemExit(f"--collide_mesh takes PLY [DX DY DZ]: 1 or 4 values, got {len(m)}")
+        try:
+            off = tuple(float(v) for v in m[1:]) if len(m) == 4 else (0.0, 0.0, 0.0)
+        except ValueError:
+            raise SystemExit(f"--collide_mesh: the offset DX DY DZ must be numbers, got {m[1:]!r}")
+        out.append((m[0], off))
+    return out
+
+
+def add_mesh_colliders(sim, args):
+    """Every --collide_mesh as a grid built on the simulator's device and placed with add_mesh_collider: --mesh_collider_res nodes
+    (default 64) along the mesh's longest axis, the box its bounds plus two voxels plus the contact thickness.  Behind enable_contact().  Returns
+    the mesh colliders' indices."""
+    from . import scene
+    from .sdf import SdfGrid
+    ids = []
+    res = getattr(args, "mesh_collider_res", None) or 64
+    for path, off in mesh_collider_specs(args):
+        try:
+            v, t = scene.read_mesh_ply(path)
+        except (OSError, ValueError) as e:
+            raise SystemExit(f"--collide_mesh: {e}")
+        h = float(sim._contact_params[3])
+        ext = float((v.max(axis=0) - v.min(axis=0)).max()) if len(v) else 0.0
+        s = (ext + 2.0 * h) / (res - 1 - 4)   # (res - 1) s = ext + 2 (2 s + h)
+        grid = SdfGrid.from_mesh(v, t, spacing=s, margin=2.0 * s + h, device=sim.device)
+        print(f"--collide_mesh {path}: {grid.triangles} triangles ({grid.dropped} dropped), grid {grid.res[0]} x {grid.res[1]} x {grid.res[2]}, "
+              f"spacing {grid.spacing:.4g}, closedness {grid.closedness:.2e}")
+        ids.append(sim.add_mesh_collider(grid, offset=off))
+    return ids
 
 
 def ball_specs(args):
@@ -160,6 +216,7 @@ def configure_contact(sim, args):
         if balls:   # behind the static colliders: --collider_color's slot order stays floor, spheres, container, boxes, capsules, then the balls
             sim.enable_bodies()
             ids.extend(sim.add_body(**b) for b in balls)
+        add_mesh_colliders(sim, args)   # slots of their own (0 .. 3): not among the indices returned
     except ValueError as e:   # a parameter out of range, a radius <= 0, a mass <= 0, a ninth collider
         raise SystemExit(f"contact: {e}")
     return ids
@@ -272,6 +329,9 @@ def configure_points(h, args):
 
 def check_overlay_args(args):
     """What configure_overlay refuses, before anything is built."""
+    mesh_collider_specs(args)
+    if args.draw_colliders and wants_contact(args) and not wants_analytic_collider(args):
+        raise SystemExit("--draw_colliders draws the analytic colliders (DESIGN.md 4.11): a --collide_mesh collides but is not drawn")
     if args.draw_colliders and not wants_contact(args):
         raise SystemExit("--draw_colliders needs --floor, --collide_sphere, --collide_inside or --ball (or --collide_box, --collide_capsule)")
     if not args.draw_colliders and (args.collider_color or args.checker is not None):
@@ -527,6 +587,10 @@ def parser():
     ap.add_argument("--contact_stiffness", type=float, default=None, help="share of a penetration removed per substep, in (0, 1] (default 0.5)")
     ap.add_argument("--contact_damping", type=float, default=None, help="share of the approach velocity removed per substep, in [0, 1] (default 0.5)")
     ap.add_argument("--friction", type=float, default=None, help="Coulomb friction coefficient of the colliders, >= 0 (default 0.5)")
+    ap.add_argument("--collide_mesh", nargs="+", action="append", default=None, metavar="PLY [DX DY DZ]",
+                    help="collide with the closed triangle mesh in PLY (write_mesh_ply's layout: main_render --save_mesh, python -m pienerf_amd.sdf --terrain), "
+                         "moved by DX DY DZ: a signed-distance grid built on the device (DESIGN.md 4.20); repeatable, at most 4")
+    ap.add_argument("--mesh_collider_res", type=int, default=None, help="nodes of a --collide_mesh grid along the mesh's longest axis (default 64)")
     ap.add_argument("--contact_thickness", type=float, default=None, help="contact begins this far outside a collider (default: sim_dx / 2)")
     ap.add_argument("--unpin", action="store_true", help="clear every pin of the cloud: the object falls (give it a --floor or a --collide_box)")
     ap.add_argument("--wind", type=float, nargs=3, default=None, metavar=("WX", "WY", "WZ"), help="a wind of this velocity blows on the object (force fields, DESIGN.md 4.15)")

@@ -177,6 +177,48 @@ def read_ply(path):
     return cols
 
 
+def read_mesh_ply(path):
+    """(vertices [V, 3] float32, triangles [T, 3] int32) of a triangle mesh in write_mesh_ply's layout: binary little endian, a vertex element that
+    begins with x, y, z (further scalar properties — normals, colours — are skipped) and a face element whose one property is a list of 3 indices
+    with a uchar count.  ValueError for anything else."""
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError(f"{path}: not a PLY file")
+        fmt, elements = None, []
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError(f"{path}: the PLY header does not end")
+            tok = line.decode().split()
+            if not tok or tok[0] == "comment":
+                continue
+            if tok[0] == "end_header":
+                break
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element":
+                elements.append((tok[1], int(tok[2]), []))
+            elif tok[0] == "property" and elements:
+                elements[-1][2].append(tok[1:])
+        if fmt != "binary_little_endian" or [e[0] for e in elements] != ["vertex", "face"]:
+            raise ValueError(f"{path}: read_mesh_ply reads binary_little_endian files with a vertex and a face element (write_mesh_ply's layout)")
+        (_, nv, vprops), (_, nf, fprops) = elements
+        if any(p[0] == "list" for p in vprops) or [p[1] for p in vprops[:3]] != ["x", "y", "z"]:
+            raise ValueError(f"{path}: the vertex element begins with the scalar properties x, y, z")
+        if len(fprops) != 1 or fprops[0][0] != "list" or fprops[0][1] != "uchar" or _PLY_NAMES.get(fprops[0][2]) not in ("i4", "u4"):
+            raise ValueError(f"{path}: the face element is `property list uchar int vertex_indices`")
+        vdt = np.dtype([(p[1], "<" + _PLY_NAMES[p[0]]) for p in vprops])
+        fdt = np.dtype([("n", "u1"), ("i", "<" + _PLY_NAMES[fprops[0][2]], (3,))])
+        vraw, fraw = f.read(nv * vdt.itemsize), f.read(nf * fdt.itemsize)
+        if len(vraw) != nv * vdt.itemsize or len(fraw) != nf * fdt.itemsize:
+            raise ValueError(f"{path}: the file ends before its {nv} vertices and {nf} faces do")
+        vert, face = np.frombuffer(vraw, dtype=vdt, count=nv), np.frombuffer(fraw, dtype=fdt, count=nf)
+    if nf and not (face["n"] == 3).all():
+        raise ValueError(f"{path}: every face must be a triangle")
+    v = np.stack([vert["x"], vert["y"], vert["z"]], axis=1).astype(np.float32)
+    return v, np.ascontiguousarray(face["i"]).astype(np.int32)
+
+
 def cloud_from_ply(path):
     c = read_ply(path)
     missing = [k for k in ("mass", "mu", "lam", "pin") if k not in c]

@@ -45,7 +45,15 @@ class StageHost:
         return tuple(st for st in self.STAGES if getattr(self, st.flag))
 
     def enabled_stage_names(self):
-        return frozenset(st.name for st in self.enabled_stages())
+        """What a capture records (_captured.Captured.stages): the enabled stages' names, and what an enabled stage adds to them while it enqueues
+        launches that a graph captured earlier lacks (contact.py: "mesh_colliders")."""
+        names = set()
+        for st in self.enabled_stages():   # a stage's mixin may name more with a method _<stage>_capture_names()
+            names.add(st.name)
+            more = getattr(self, f"_{st.name}_capture_names", None)
+            if more is not None:
+                names.update(more())
+        return frozenset(names)
 
     # ------------------------------------------------------------------ guards
     def _stage_state(self, st, gpu=True):

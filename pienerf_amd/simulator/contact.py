@@ -9,7 +9,8 @@ from ._stage import Stage, _vec3, torchfloat
 
 __all__ = ["CONTACT_SLOTS", "CONTACT_EMPTY", "CONTACT_PLANE", "CONTACT_SPHERE", "CONTACT_CONTAINER", "CONTACT_BOX", "CONTACT_CAPSULE",
            "CONTACT_COLLIDER_DTYPE", "CONTACT_STATE_DTYPE", "CONTACT_STATE_DOUBLES", "contact_params", "contact_plane", "contact_sphere", "contact_box",
-           "contact_capsule", "pack_contact_state", "ContactMixin"]   # what solver.py re-exports
+           "contact_capsule", "pack_contact_state", "SDF_SLOTS", "SDF_SLOT_DTYPE", "SDF_STATE_DTYPE", "pack_sdf_state",
+           "ContactMixin"]   # what solver.py re-exports
 
 CONTACT_SLOTS = 8          # pn_contact_state's collider slots (include/pienerf_hip.h: PN_CONTACT_SLOTS)
 CONTACT_EMPTY, CONTACT_PLANE, CONTACT_SPHERE, CONTACT_CONTAINER = 0, 1, 2, 3
@@ -19,6 +20,11 @@ CONTACT_COLLIDER_DTYPE = np.dtype([("type", "<i4"), ("reserved", "<i4"), ("p", "
 CONTACT_STATE_DTYPE = np.dtype([("active", "<i4"), ("n", "<i4"), ("kappa", "<f8"), ("beta", "<f8"), ("mu", "<f8"), ("h", "<f8"),
                                 ("c", CONTACT_COLLIDER_DTYPE, (CONTACT_SLOTS,))])
 CONTACT_STATE_DOUBLES = CONTACT_STATE_DTYPE.itemsize // 8
+# mesh colliders: pn_sdf_slot / pn_sdf_state (include/pienerf_hip.h) as numpy records, 80 and 328 bytes = pn_sim_sdf_bytes(), checked
+# in _alloc_sdf.  The contact stage's optional second state: allocated with the first mesh collider, never before
+SDF_SLOTS = 4              # PN_SDF_SLOTS
+SDF_SLOT_DTYPE = np.dtype([("grid", "<u8"), ("nx", "<i4"), ("ny", "<i4"), ("nz", "<i4"), ("reserved", "<i4"), ("lo", "<f8", (3,)), ("s", "<f8"), ("v", "<f8", (3,))])
+SDF_STATE_DTYPE = np.dtype([("n", "<i4"), ("reserved", "<i4"), ("c", SDF_SLOT_DTYPE, (SDF_SLOTS,))])
 
 STAGE = Stage(name="contact", flag="contact_enabled", state="_contact_state", subject="contact is", owner="the contact state", enable="enable_contact",
               struct="pn_contact_state", nbytes=CONTACT_STATE_DOUBLES * 8, sized_by="solver.py allocates", init="_init_contact", alloc="_alloc_contact",
@@ -114,8 +120,28 @@ def pack_contact_state(active, params, colliders):
     return st.tobytes()
 
 
+def pack_sdf_state(colliders):
+    """The bytes of a pn_sdf_state holding `colliders` = SDF_SLOTS entries, each None or (grid, offset3, velocity3) with grid an SdfGrid: what the
+    device state holds after the setters (n = 1 + the highest slot in use; a slot's lo is the grid's lo plus the offset)."""
+    st = np.zeros((), SDF_STATE_DTYPE)
+    assert len(colliders) == SDF_SLOTS
+    n = 0
+    for i, c in enumerate(colliders):
+        if c is None:
+            continue
+        g, off, vel = c
+        nz, ny, nx = g.shape
+        r = st["c"][i]
+        r["grid"], r["nx"], r["ny"], r["nz"], r["lo"], r["s"], r["v"] = g.values.data_ptr(), nx, ny, nz, g.lo + off, g.spacing, vel
+        n = i + 1
+    st["n"] = n
+    return st.tobytes()
+
+
 class ContactMixin:
     def _init_contact(self):
+        self._sdf_state = None
+        self._mesh_colliders = [None] * SDF_SLOTS   # (SdfGrid, offset, velocity): the host mirror, and what keeps a placed grid's memory alive
         self.contact_enabled = False
         self._contact_state = self._rhs_contact = self._contact_accel = None
         self._contact_params = None
@@ -141,6 +167,8 @@ class ContactMixin:
         for i, c in enumerate(self._colliders):
             if c is not None:
                 self._upload_collider(i)
+        if any(c is not None for c in self._mesh_colliders):
+            self._alloc_sdf()
 
     def _upload_contact_params(self):
         p = np.ascontiguousarray(self._contact_params)
@@ -272,10 +300,107 @@ class ContactMixin:
         """The type of every collider slot (CONTACT_EMPTY / _PLANE / _SPHERE / _CONTAINER / _BOX / _CAPSULE), from the host mirror."""
         return [CONTACT_EMPTY if c is None else int(c[0]) for c in self._colliders]
 
+    # ------------------------------------------------------------------ mesh colliders: signed-distance grids (DESIGN.md 4.20)
+    def _contact_capture_names(self):
+        """StageHost.enabled_stage_names(): while a mesh collider exists the stage enqueues one launch more, which a graph captured before lacks."""
+        return ("mesh_colliders",) if any(c is not None for c in self._mesh_colliders) else ()
+
+    def _alloc_sdf(self):
+        nb = int(lib().pn_sim_sdf_bytes())
+        if nb != SDF_STATE_DTYPE.itemsize:
+            raise RuntimeError(f"libpienerf_hip.so's pn_sdf_state has {nb} bytes, contact.py lays out {SDF_STATE_DTYPE.itemsize}")
+        self._sdf_state = torch.zeros(SDF_STATE_DTYPE.itemsize // 8, dtype=torchfloat, device=self.device)
+        for i, c in enumerate(self._mesh_colliders):
+            if c is not None:
+                self._upload_mesh_collider(i)
+
+    def _upload_mesh_collider(self, i):
+        c = self._mesh_colliders[i]
+        if c is not None and c[0].values.device != self._sdf_state.device:
+            self._mesh_colliders[i] = None
+            raise ValueError(f"contact: a mesh collider's grid lives on {c[0].values.device}, the simulator on {self._sdf_state.device}")
+        with self._on_force_stream():
+            if c is None:
+                check(lib().pn_sim_sdf_set_collider(ptr(self._sdf_state), int(i), None, 0, 0, 0, None, stream_ptr()), "sim_sdf_set_collider")
+                return
+            g, off, vel = c
+            g.values.record_stream(torch.cuda.current_stream(self.device))   # force_stream (or the current one): the stream of eager substeps
+            nz, ny, nx = g.shape
+            geom = np.ascontiguousarray(np.concatenate([g.lo + off, [g.spacing], vel]), dtype=np.float64)
+            check(lib().pn_sim_sdf_set_collider(ptr(self._sdf_state), int(i), ptr(g.values), nx, ny, nz, geom.ctypes.data, stream_ptr()),
+                  "sim_sdf_set_collider")
+
+    def _put_mesh_collider(self, i, c):
+        self._mesh_colliders[i] = c
+        if self._contact_state is not None:   # on a GPU and initialised: the second state comes with the first mesh collider
+            if self._sdf_state is None:
+                self._alloc_sdf()
+            else:
+                self._upload_mesh_collider(i)   # on force_stream: the change lands between two substeps
+        return i
+
+    def add_mesh_collider(self, grid, offset=(0.0, 0.0, 0.0), velocity=None):
+        """A static solid given by a signed-distance grid (pienerf_amd.sdf.SdfGrid: from_mesh, from_function), placed at `offset` from where it was
+        built: contact's own response, with its parameters, at the trilinear distance and gradient of the grid (include/pienerf_hip.h:
+        pn_sim_contact_sdf_rhs has the law).  A point outside the grid's box gets nothing from it.  `velocity` (None: at rest) is the collider's own,
+        for the relative velocity of damping and friction; the solid moves only when set_mesh_collider moves it.  Translation only: rotate or scale
+        the mesh before building.  The rigid balls (bodies.py) ignore mesh colliders, and the one-launch form of the stage does not exist with
+        them.  Returns the collider's index 0..3; ValueError for a fifth, a grid that is not an SdfGrid or a non-finite offset."""
+        self._stage_state(STAGE, gpu=False)
+        from ..sdf import SdfGrid
+        if not isinstance(grid, SdfGrid):
+            raise ValueError(f"contact: a mesh collider is an SdfGrid (pienerf_amd.sdf), got {type(grid).__name__}")
+        c = (grid, _vec3(offset, "a mesh collider's offset"), _vec3(velocity, "a collider's velocity") if velocity is not None else np.zeros(3))
+        for i, have in enumerate(self._mesh_colliders):
+            if have is None:
+                return self._put_mesh_collider(i, c)
+        raise ValueError(f"contact: all {SDF_SLOTS} mesh collider slots are in use (remove_mesh_collider frees one)")
+
+    def _mesh_slot(self, index):
+        self._stage_state(STAGE, gpu=False)
+        i = int(index)
+        if not 0 <= i < SDF_SLOTS or self._mesh_colliders[i] is None:
+            raise ValueError(f"contact: there is no mesh collider {index!r}")
+        return i
+
+    def set_mesh_collider(self, index, offset=None, velocity=None):
+        """Moves mesh collider `index` to `offset` and / or gives it `velocity`, from the next substep on (None keeps a value): a scripted translation,
+        followed by captured graphs without a recapture.  ValueError for an index without a mesh collider or a non-finite value."""
+        i = self._mesh_slot(index)
+        g, off, vel = self._mesh_colliders[i]
+        self._put_mesh_collider(i, (g, off if offset is None else _vec3(offset, "a mesh collider's offset"),
+                                    vel if velocity is None else _vec3(velocity, "a collider's velocity")))
+
+    def remove_mesh_collider(self, index):
+        """Empties the slot: the grid acts on no further substep, its index may be handed out again.  The simulator drops its reference to the grid
+        with it.  Substeps already enqueued on other streams than force_stream (a captured graph's, a pipeline's) may still read the grid: wait for
+        them (synchronize) before the last reference to the grid goes."""
+        self._put_mesh_collider(self._mesh_slot(index), None)
+
+    def mesh_collider_state(self):
+        """The pn_sdf_state on the device (41 doubles), the simulator's own buffer, or None while no mesh collider was ever added on the device.
+        RuntimeError before enable_contact()."""
+        self._stage_state(STAGE, gpu=False)
+        return self._sdf_state
+
+    def mesh_collider_state_bytes(self):
+        """What the device state holds, packed from the mirror kept here (pack_sdf_state): tests compare the device's bytes with it."""
+        self._stage_state(STAGE, gpu=False)
+        return pack_sdf_state(self._mesh_colliders)
+
     def _enqueue_contact_rhs(self, rhs_in, one_launch=False):
         """_rhs_contact = rhs_in + the contact term of the current dof / dof_vel, on the current stream.  Returns _rhs_contact.  Two launches: the law at
         every point into _contact_accel, then the per-kernel sums (the measured faster form).  one_launch=True (tools/time_contact.py, tests):
-        the form in which every entry evaluates its point itself — the same bits in _rhs_contact, _contact_accel left as it is."""
+        the form in which every entry evaluates its point itself — the same bits in _rhs_contact, _contact_accel left as it is.  With a mesh collider
+        present: three launches, the grids' terms added to _contact_accel between the two (pn_sim_contact_sdf_rhs); one_launch then raises."""
+        if any(c is not None for c in self._mesh_colliders):
+            if one_launch:
+                raise RuntimeError("contact: the one-launch form does not evaluate mesh colliders (remove_mesh_collider first)")
+            check(lib().pn_sim_contact_sdf_rhs(self.n_k, self.n_IP, ptr(self._stage_state(STAGE)), ptr(self._sdf_state), float(self.dt), float(self.dx),
+                                               ptr(self.dof), ptr(self.dof_vel), ptr(self.IP_kernel), ptr(self.IP_rho), ptr(self.IP_Nx), ptr(self.kernel_bg),
+                                               ptr(self.kernel_cnt), ptr(self.buffer), ptr(self.Nx_csr), ptr(rhs_in), ptr(self._rhs_contact),
+                                               ptr(self._contact_accel), stream_ptr()), "sim_contact_sdf_rhs")
+            return self._rhs_contact
         check(lib().pn_sim_contact_rhs(self.n_k, self.n_IP, ptr(self._stage_state(STAGE)), float(self.dt), float(self.dx), ptr(self.dof), ptr(self.dof_vel),
                                        ptr(self.IP_kernel), ptr(self.IP_rho), ptr(self.IP_Nx), ptr(self.kernel_bg), ptr(self.kernel_cnt), ptr(self.buffer),
                                        ptr(self.Nx_csr), ptr(rhs_in), ptr(self._rhs_contact), None if one_launch else ptr(self._contact_accel), stream_ptr()),
